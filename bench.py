@@ -19,7 +19,9 @@ runs on 32 injected boxes per image — no stage is skipped.
 With N > 1 every rank runs its own shard of images (weak scaling) and the per-image result records
 are exchanged by ONE RCCL all_gather per step, inside the timed region.
 
-Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).
+Prints ONE JSON line on rank 0 (see README/DESIGN.md for the fields).  A plain run sets up, warms up, times --steps steps and
+prints the headline; --full adds the self-check, side loops, per-kernel roofline and CPU baseline; --dump-outputs DIR writes what
+the last timed step computed.
 """
 from __future__ import annotations
 
@@ -60,7 +62,14 @@ def parse():
     ap.add_argument("--batch", type=int, default=BATCH)
     ap.add_argument("--side", type=int, default=SIDE)
     ap.add_argument("--rois", type=int, default=ROIS)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the pipelined == synchronous self-check, the side loops (from-host, runner policy, "
+                         "fp32 MFMA only, latency), the metered steps behind `roofline` / `conv_bound_roofline` and the CPU baseline.  "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32; at most 64 MB "
+                         "in all, larger outputs as a fixed seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp16", "fp16s"],
                     help="fp32 (default: the reference's arithmetic, what the metric is quoted on) or fp16 = BASELINE configs[4]'s "
                          "precision: conv / linear operands rounded to fp16 on the fp16 matrix cores, fp32 accumulate and "
@@ -72,21 +81,24 @@ def parse():
                          "(1 = one step at a time: 204 vs 210 images/s on MI355X)")
     ap.add_argument("--workload", default="e2e", choices=["e2e", "backbone"],
                     help="e2e = BASELINE configs[2] (default, the metric's config); backbone = configs[1] (ResNet50-FPN only)")
-    ap.add_argument("--conv-table", default="", help="write the per-launch conv table of the instrumented step here")
+    ap.add_argument("--conv-table", default="", help="(--full) write the per-launch conv table of the instrumented step here")
     ap.add_argument("--cpu-side", type=int, default=SIDE, help="image side of the bounded CPU-baseline sample")
     ap.add_argument("--from-host", action="store_true",
                     help="time ONLY the from-host variant as the main loop: every step starts from uint8 HWC images in pinned "
                          "host memory (H2D copy + on-device u8->f32 CHW conversion inside the step, GlassRunner's front-end). "
                          "Without this flag the contract's HBM-resident rate is `value` and the from-host rate of a second "
                          "timed loop is reported next to it (`from_host`).")
-    ap.add_argument("--no-extras", action="store_true", help="skip the from-host and latency loops (value only)")
+    ap.add_argument("--no-extras", action="store_true", help="(--full) skip the from-host and latency loops")
     ap.add_argument("--runner-policy", action="store_true",
                     help="time the GlassRunner path as the main loop: uint8 HWC host images -> H2D -> fused convert + bilinear resize "
                          "by the reference's policy (glass_runner.py:111-148: a 1000 x 1000 image under the ICDAR15 cfg's "
                          "MIN_SIZE_TEST 1200 is upscaled x1.2 to 1200 x 1200, padded to 1216 x 1216: 504 GMAC, BASELINE.md section 3) "
                          "-> model -> results un-scaled by 1 / 1.2.  Without the flag this leg is reported as `runner_policy` next "
                          "to `from_host`.  PCIe-inclusive and a larger workload than the metric's: never `value` of the headline.")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.conv_table and not args.full:
+        ap.error("--conv-table needs --full (the per-launch table comes from the metered steps)")
+    return args
 
 
 class ConvMeter:
@@ -352,6 +364,45 @@ def self_launch(args) -> int:
     return launch_local_ranks([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], args.gpus)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def last_step_outputs(records, outs):
+    """what the last timed step computed, as {name: tensor}: the gathered word records the step returns and the model's padded
+    batch behind them (`inference_g(...).batch`: boxes, scores, orientations, counts, character probabilities of the recognised
+    RoIs); for --workload backbone the FPN maps.  Slots past an image's count are padding the step does not write: zeroed."""
+    if "det" not in outs:
+        return dict(outs)
+    det = outs["det"]
+    counts = det.counts_dev.long()
+
+    def valid(x):
+        keep = torch.arange(x.shape[1], device=x.device)[None, :] < counts.to(x.device)[:, None]
+        return torch.where(keep.view(*keep.shape, *[1] * (x.dim() - 2)), x, torch.zeros((), dtype=x.dtype, device=x.device))
+
+    got = {"word_records": records, "detection_counts": counts}
+    for name, x in (("detection_boxes", det.boxes), ("detection_scores", det.scores), ("detection_orientations", det.orient),
+                    ("text_probs", det.text)):
+        if x is not None:
+            got[name] = x if (name == "text_probs" and x.dim() == 3) else valid(x)     # (text: padded [N,K,T,C] or packed [sum counts,T,C])
+    return got
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """--dump-outputs: {name: tensor} -> out_dir/<name>.npy in float32.  When the whole exceeds DUMP_BUDGET_BYTES every array is cut
+    to the same share of its elements (flattened), at positions drawn by a generator of fixed seed: two runs with the same
+    arguments compare element for element."""
+    import numpy as np
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    share = min(1.0, (DUMP_BUDGET_BYTES - 4096 * len(arrays)) / total) if total else 1.0     # (4 KiB: room for each .npy header)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if share < 1.0:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(0).integers(0, a.size, int(a.size * share)))]
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
+
+
 _REAL_STDOUT = None
 
 
@@ -449,6 +500,7 @@ def main():
     import glass_amd
     from glass_amd.utils.host import limit_host_threads
     limit_host_threads()          # before the first CPU tensor op: the host side is launch glue (utils/host.py)
+    from glass_amd._lib import source_sha16
     from glass_amd.config import get_glass_cfg
     from glass_amd.distributed import all_gather_records, pack_words
     from glass_amd.postprocess import build_post_processor
@@ -474,8 +526,11 @@ def main():
     images, inputs = image_sets[0], input_sets[0]
     # GlassRunner's front-end (reference glass_runner.py:123-148): uint8 HWC image on the host -> device -> float CHW.
     # The synthetic float images above hold integer values 0..255, so the uint8 route gives bit-identical inputs.
-    host_u8_sets = [[im.permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).cpu().contiguous().pin_memory() for im in ims]
-                    for ims in image_sets]
+    # (Only the legs that start from the host use them: --from-host, --runner-policy and the side loops of --full.)
+    host_u8_sets = None
+    if args.full or args.from_host or args.runner_policy:
+        host_u8_sets = [[im.permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).cpu().contiguous().pin_memory() for im in ims]
+                        for ims in image_sets]
     max_det = cfg.TEST.DETECTIONS_PER_IMAGE
     post = build_post_processor(cfg)                              # PostProcessorAcademic (device kernel)
     out_sizes = [(args.side, args.side)] * B
@@ -499,9 +554,11 @@ def main():
         policy_boxes = [prepare_injected_boxes(bs, dev) for bs in policy_boxes]
     policy_scale = torch.tensor([[1.0 / policy_ratio, 1.0 / policy_ratio]] * B, dtype=torch.float32, device=dev)
 
-    def local_step_g(from_host=False, s=0, keep=None, policy=False):
-        """one step (input set `s`) as a generator (glass_amd/utils/pipeline.py): yields where the host reads counts back"""
-        host_u8, boxes = host_u8_sets[s], box_sets[s]
+    def local_step_g(from_host=False, s=0, keep=None, policy=False, outs=None):
+        """one step (input set `s`) as a generator (glass_amd/utils/pipeline.py): yields where the host reads counts back.
+        `outs` (a dict): receives references to the step's device results for --dump-outputs (no copy, no extra launch)"""
+        boxes = box_sets[s]
+        host_u8 = host_u8_sets[s] if host_u8_sets is not None else None
         scale_xy = None
         if policy:
             # the runner's front end: H2D of the uint8 HWC images + ONE fused convert + bilinear resize kernel to the policy size;
@@ -516,7 +573,9 @@ def main():
         else:
             step_inputs = input_sets[s]
         if args.workload == "backbone":                           # BASELINE configs[1]: trunk + FPN only
-            model.backbone.forward_nhwc(il.nhwc4)                 # (the layers' weights carry the model's precision)
+            feats = model.backbone.forward_nhwc(il.nhwc4)         # (the layers' weights carry the model's precision)
+            if outs is not None:
+                outs.update({"fpn_" + k: v for k, v in feats.items()})
             return torch.zeros((B, 1), device=dev)
             yield                                                 # pragma: no cover (makes this a generator)
         out = yield from model.inference_g(step_inputs, override_boxes=boxes)   # list[{"instances": Instances}] (views)
@@ -526,10 +585,12 @@ def main():
                                                  {"orientations": det.orient})
         if keep is not None:                                      # the un-timed self-check: the step's character probabilities
             keep.append(det.text.clone())
+        if outs is not None:
+            outs["det"] = det
         return pack_words(words.words, max_det, steps_txt)        # fixed-size per-image word records
 
-    def step_g(from_host=False, s=0, keep=None, policy=args.runner_policy):
-        rec = yield from local_step_g(from_host, s, keep, policy)
+    def step_g(from_host=False, s=0, keep=None, policy=args.runner_policy, outs=None):
+        rec = yield from local_step_g(from_host, s, keep, policy, outs)
         if dist is not None and backend != "nccl":
             return all_gather_records(rec.cpu(), rows=B)
         return all_gather_records(rec, rows=B)                    # every rank holds B images: no count exchange needed
@@ -537,11 +598,12 @@ def main():
     def local_step(s=0):
         return drive(local_step_g(s=s, policy=args.runner_policy))
 
-    def run_steps(n, from_host=args.from_host, depth=None, first=0, policy=args.runner_policy):
+    def run_steps(n, from_host=args.from_host, depth=None, first=0, policy=args.runner_policy, last_outs=None):
         """n steps over the input sets in turn, `--pipeline` of them in flight (each on its own stream; host segments
-        interleaved in a fixed order, so every rank issues its all_gathers in the same order)"""
-        return run_pipelined([(lambda s=(first + i) % NSETS: step_g(from_host, s, None, policy)) for i in range(n)],
-                             depth=depth or args.pipeline, device=dev)
+        interleaved in a fixed order, so every rank issues its all_gathers in the same order).  `last_outs`: the last step's
+        `outs` (local_step_g)"""
+        return run_pipelined([(lambda i=i, s=(first + i) % NSETS: step_g(from_host, s, None, policy, last_outs if i == n - 1 else None))
+                              for i in range(n)], depth=depth or args.pipeline, device=dev)
 
     def barrier():
         torch.cuda.synchronize()
@@ -552,10 +614,10 @@ def main():
     # not part of W or K: the first step on each pipeline stream fills that stream's allocator pool (hipMalloc); one step
     # per stream so that a small --warmup cannot leave a cold one.  (Weights were packed in load_state_dict.)
     run_steps(args.pipeline)
-    # once per run, outside the timed region: every input set's PIPELINED step returns bit for bit the record of its
+    # --full, outside the timed region: every input set's PIPELINED step returns bit for bit the record of its
     # synchronous run (per-step state / stream hazards would show here; tests/test_gpu_z_pipeline.py holds it for small shapes)
     pipelined_equals_sync = None
-    if args.workload == "e2e":
+    if args.full and args.workload == "e2e":
         sync_txt = [[] for _ in range(NSETS)]
         sync_recs = [drive(step_g(args.from_host, s, sync_txt[s])) for s in range(NSETS)]
         pipe_txt = [[] for _ in range(2 * NSETS)]
@@ -584,8 +646,9 @@ def main():
         import cProfile
         prof = cProfile.Profile()
         prof.enable()
+    step_outs = {} if args.dump_outputs else None
     t0 = time.perf_counter()
-    timed_results = run_steps(args.steps)
+    timed_results = run_steps(args.steps, last_outs=step_outs)
     barrier()
     dt = time.perf_counter() - t0
     if prof is not None:
@@ -598,6 +661,8 @@ def main():
     if args.workload == "e2e":
         assert last.dim() == 3 and last.shape[0] * last.shape[1] == world * B, (tuple(last.shape), world, B)
         assert bool((last[..., 0] >= 0).all()) and bool((last[..., 0] <= max_det).all()), "a gathered record carries a bad word count"
+    if step_outs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(last, step_outs))
     if dist is not None:
         cdev = dev if backend == "nccl" else "cpu"
         t = torch.tensor([dt], dtype=torch.float64, device=cdev)
@@ -634,7 +699,7 @@ def main():
         return d
 
     extras = {}
-    if not args.no_extras and args.workload == "e2e":
+    if args.full and not args.no_extras and args.workload == "e2e":
         n_x = max(4, min(args.steps, 20))
         if not args.from_host:
             d = timed_loop(n_x, from_host=True)
@@ -672,100 +737,100 @@ def main():
 
     line = None
     if rank == 0:
-        # dominant kernel: three extra instrumented steps, outside the timed region
-        # (rank-local: must not enter a collective the other ranks are not in)
-        # (serial execution: the product overlaps the two halves of the local extractor on two streams,
-        #  which would inflate per-kernel event times)
-        two = model.roi_heads.two_stream_local
-        model.roi_heads.two_stream_local = False
-        with ConvMeter(K) as meter:
-            for rep in range(3):                                  # per-launch median over three identical steps
-                if rep:
-                    meter.new_step()
-                local_step()
-            fam = meter.summary()
-            if args.conv_table:
-                with open(args.conv_table, "w") as f:
-                    for p_, xs, ws, st, res, ms, tf in meter.table():
-                        f.write(f"{ms:8.3f} ms {tf:7.1f} TF/s  {p_:11s} x{list(xs)} -> Cout {ws[0]} k{ws[1]}x{ws[2]} s{st}"
-                                f"{' +res' if res else ''}\n")
-        # the same three metered steps with the 1x1 layers on the fp32 MFMA: the split kernel sits at the package power cap and
-        # lowers the clock the WHOLE step is granted, so the other families' per-launch times (and the dominant kernel's
-        # `frac`) read ~3 % worse beside it than they do without it - both readings go on the line
-        fam_fp32 = None
-        if args.precision == "fp32" and getattr(model.routing, "split", 0):
-            split_was = model.routing.split
-            model.routing.split = 0
-            try:
-                with ConvMeter(K) as meter0:
-                    for rep in range(3):
-                        if rep:
-                            meter0.new_step()
-                        local_step()
-                    fam_fp32 = meter0.summary()
-            finally:
-                model.routing.split = split_was
-        model.roi_heads.two_stream_local = two
-        conv_ms = sum(f["ms"] for f in fam.values())
-        conv_flops = sum(f["algo_flops"] for f in fam.values())
-        n_launch = sum(f["launches"] for f in fam.values())
-        KNAME = {"winograd43": "conv3x3_wino43_f32 (Winograd F(4x4,3x3), fp32 MFMA 16x16x4, 16 tiles x 128 channels per workgroup)",
-                 "winograd128": "conv3x3_wino128_f32 (Winograd F(2x2,3x3), fp32 MFMA, 32 tiles x 128 channels per workgroup)",
-                 "winograd": "conv3x3_wino_f32 (Winograd F(2x2,3x3), fp32 MFMA, 64 tiles x 64 channels per workgroup)",
-                 "pointwise": "conv1x1_pw_f32 (fp32 MFMA 16x16x4 weight-streaming 1x1 GEMM)",
-                 "pointwise_split": "conv1x1_pw_split (1x1 GEMM, exact fp32 products as nine bf16 piece products: bf16 MFMA 16x16x32, fp32 accumulate; executed_* count the bf16 MFMA FLOP against the bf16 peak)",
-                 "direct": "conv_igemm_f32 (fp32 MFMA implicit-GEMM conv/linear)",
-                 "direct_fp16": "conv_igemm_f32<..., HALF> (fp16 MFMA implicit-GEMM conv/linear, fp32 accumulate)",
-                 "packed_fp16": "conv_h16_kernel (fp16 MFMA 16x16x32 weight-streaming implicit-GEMM conv on fp16 tensors, fp32 accumulate)",
-                 "fused_stem": "backbone_stem_fused_kernel + local_stem_fused_kernel (conv + ReLU + max-pool fused stems, fp32 MFMA 32x32x2)"}
-        PKEY = {"winograd43": "conv3x3_wino43_f32", "winograd128": "conv3x3_wino128_f32", "winograd": "conv3x3_wino_f32", "pointwise": "conv1x1_pw_f32", "pointwise_split": "conv1x1_pw_split", "direct": "conv_igemm_f32_64x64",     # direct: its busiest instantiation
-                "direct_fp16": "conv_igemm_f16", "packed_fp16": "conv_h16_kernel", "fused_stem": "backbone_stem_fused_kernel"}
-        PEAK = PEAK_DEFAULT = FP32_MFMA_PEAK_TFLOPS if args.precision == "fp32" else FP16_MFMA_PEAK_TFLOPS
-        dom = max(fam, key=lambda k: fam[k]["ms"])            # the dominant kernel by time
-        # PMC passes kept under profiles/ (FETCH_SIZE / WRITE_SIZE / SQ_VALU_MFMA_BUSY_CYCLES in separate
-        # rocprofv3 --pmc runs, gfx950 x2 read correction applied; scripts/pmc_make_summary.py)
-        pmc_all, pmc_file, pmc_note = {}, None, "no PMC summary under profiles/"
-        from glass_amd._lib import source_sha16
-        import glob
-        # fp32: r*_pmc_conv_summary.json; the fp16-storage mode has its own passes (scripts/collect_profiles.sh step 3b)
-        pmc_glob = "r*_pmc_conv_summary.json" if args.precision == "fp32" else f"r*_pmc_{args.precision}_summary.json"
-        for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", pmc_glob)), reverse=True):
-            with open(cand) as f:
-                js = json.load(f)
-            if js.get("lib_source_sha16") == source_sha16():
-                pmc_all, pmc_file = js, os.path.relpath(cand, ROOT)
-                pmc_note = f"HBM bytes/launch of this kernel, PMC ({pmc_file}; taken with this library: sha {source_sha16()})"
-                break
-            pmc_note = (f"null: {os.path.relpath(cand, ROOT)} was taken with library sha {js.get('lib_source_sha16')}, this run uses "
-                        f"{source_sha16()} - re-run scripts/collect_profiles.sh")
+        if args.full:
+            # dominant kernel: three extra instrumented steps, outside the timed region
+            # (rank-local: must not enter a collective the other ranks are not in)
+            # (serial execution: the product overlaps the two halves of the local extractor on two streams,
+            #  which would inflate per-kernel event times)
+            two = model.roi_heads.two_stream_local
+            model.roi_heads.two_stream_local = False
+            with ConvMeter(K) as meter:
+                for rep in range(3):                                  # per-launch median over three identical steps
+                    if rep:
+                        meter.new_step()
+                    local_step()
+                fam = meter.summary()
+                if args.conv_table:
+                    with open(args.conv_table, "w") as f:
+                        for p_, xs, ws, st, res, ms, tf in meter.table():
+                            f.write(f"{ms:8.3f} ms {tf:7.1f} TF/s  {p_:11s} x{list(xs)} -> Cout {ws[0]} k{ws[1]}x{ws[2]} s{st}"
+                                    f"{' +res' if res else ''}\n")
+            # the same three metered steps with the 1x1 layers on the fp32 MFMA: the split kernel sits at the package power cap and
+            # lowers the clock the WHOLE step is granted, so the other families' per-launch times (and the dominant kernel's
+            # `frac`) read ~3 % worse beside it than they do without it - both readings go on the line
+            fam_fp32 = None
+            if args.precision == "fp32" and getattr(model.routing, "split", 0):
+                split_was = model.routing.split
+                model.routing.split = 0
+                try:
+                    with ConvMeter(K) as meter0:
+                        for rep in range(3):
+                            if rep:
+                                meter0.new_step()
+                            local_step()
+                        fam_fp32 = meter0.summary()
+                finally:
+                    model.routing.split = split_was
+            model.roi_heads.two_stream_local = two
+            conv_ms = sum(f["ms"] for f in fam.values())
+            conv_flops = sum(f["algo_flops"] for f in fam.values())
+            n_launch = sum(f["launches"] for f in fam.values())
+            KNAME = {"winograd43": "conv3x3_wino43_f32 (Winograd F(4x4,3x3), fp32 MFMA 16x16x4, 16 tiles x 128 channels per workgroup)",
+                     "winograd128": "conv3x3_wino128_f32 (Winograd F(2x2,3x3), fp32 MFMA, 32 tiles x 128 channels per workgroup)",
+                     "winograd": "conv3x3_wino_f32 (Winograd F(2x2,3x3), fp32 MFMA, 64 tiles x 64 channels per workgroup)",
+                     "pointwise": "conv1x1_pw_f32 (fp32 MFMA 16x16x4 weight-streaming 1x1 GEMM)",
+                     "pointwise_split": "conv1x1_pw_split (1x1 GEMM, exact fp32 products as nine bf16 piece products: bf16 MFMA 16x16x32, fp32 accumulate; executed_* count the bf16 MFMA FLOP against the bf16 peak)",
+                     "direct": "conv_igemm_f32 (fp32 MFMA implicit-GEMM conv/linear)",
+                     "direct_fp16": "conv_igemm_f32<..., HALF> (fp16 MFMA implicit-GEMM conv/linear, fp32 accumulate)",
+                     "packed_fp16": "conv_h16_kernel (fp16 MFMA 16x16x32 weight-streaming implicit-GEMM conv on fp16 tensors, fp32 accumulate)",
+                     "fused_stem": "backbone_stem_fused_kernel + local_stem_fused_kernel (conv + ReLU + max-pool fused stems, fp32 MFMA 32x32x2)"}
+            PKEY = {"winograd43": "conv3x3_wino43_f32", "winograd128": "conv3x3_wino128_f32", "winograd": "conv3x3_wino_f32", "pointwise": "conv1x1_pw_f32", "pointwise_split": "conv1x1_pw_split", "direct": "conv_igemm_f32_64x64",     # direct: its busiest instantiation
+                    "direct_fp16": "conv_igemm_f16", "packed_fp16": "conv_h16_kernel", "fused_stem": "backbone_stem_fused_kernel"}
+            PEAK = PEAK_DEFAULT = FP32_MFMA_PEAK_TFLOPS if args.precision == "fp32" else FP16_MFMA_PEAK_TFLOPS
+            dom = max(fam, key=lambda k: fam[k]["ms"])            # the dominant kernel by time
+            # PMC passes kept under profiles/ (FETCH_SIZE / WRITE_SIZE / SQ_VALU_MFMA_BUSY_CYCLES in separate
+            # rocprofv3 --pmc runs, gfx950 x2 read correction applied; scripts/pmc_make_summary.py)
+            pmc_all, pmc_file, pmc_note = {}, None, "no PMC summary under profiles/"
+            import glob
+            # fp32: r*_pmc_conv_summary.json; the fp16-storage mode has its own passes (scripts/collect_profiles.sh step 3b)
+            pmc_glob = "r*_pmc_conv_summary.json" if args.precision == "fp32" else f"r*_pmc_{args.precision}_summary.json"
+            for cand in sorted(glob.glob(os.path.join(ROOT, "profiles", pmc_glob)), reverse=True):
+                with open(cand) as f:
+                    js = json.load(f)
+                if js.get("lib_source_sha16") == source_sha16():
+                    pmc_all, pmc_file = js, os.path.relpath(cand, ROOT)
+                    pmc_note = f"HBM bytes/launch of this kernel, PMC ({pmc_file}; taken with this library: sha {source_sha16()})"
+                    break
+                pmc_note = (f"null: {os.path.relpath(cand, ROOT)} was taken with library sha {js.get('lib_source_sha16')}, this run uses "
+                            f"{source_sha16()} - re-run scripts/collect_profiles.sh")
 
-        def fam_entry(k):
-            f = fam[k]
-            if f["launches"] == 0:
-                return None
-            sec = f["ms"] * 1e-3
-            PEAK = FP16_MFMA_PEAK_TFLOPS if k == "pointwise_split" else PEAK_DEFAULT      # bf16 peak = fp16 peak
-            pj = pmc_all.get(PKEY[k], {}) if isinstance(pmc_all.get(PKEY[k], {}), dict) else {}
-            return {"kernel": KNAME[k], "launches_per_step": f["launches"], "kernel_ms_per_step": f["ms"],
-                    "avg_launch_ms": f["ms"] / f["launches"],
-                    "executed_tflops": f["exec_flops"] / sec / 1e12, "executed_frac": f["exec_flops"] / sec / 1e12 / PEAK,
-                    "algorithmic_tflops": f["algo_flops"] / sec / 1e12,
-                    "algorithmic_frac": f["algo_flops"] / sec / 1e12 / PEAK_DEFAULT,
-                    "algorithmic_gflop_per_launch": f["algo_flops"] / f["launches"] / 1e9,
-                    "traffic": pj.get("hbm_bytes_per_launch_corrected"), "mfma_util_percent_pmc": pj.get("MfmaUtil_percent"),
-                    # the same family's weighted average launch in the committed rocprofv3 --kernel-trace --stats table
-                    # (profiles/rNN_kernel_stats_serial.txt, folded into the PMC summary of this library): compare with
-                    # avg_launch_ms * 1e3, which comes from HIP events inside this very run
-                    "rocprof_avg_us": pj.get("rocprof_avg_us")}
+            def fam_entry(k):
+                f = fam[k]
+                if f["launches"] == 0:
+                    return None
+                sec = f["ms"] * 1e-3
+                PEAK = FP16_MFMA_PEAK_TFLOPS if k == "pointwise_split" else PEAK_DEFAULT      # bf16 peak = fp16 peak
+                pj = pmc_all.get(PKEY[k], {}) if isinstance(pmc_all.get(PKEY[k], {}), dict) else {}
+                return {"kernel": KNAME[k], "launches_per_step": f["launches"], "kernel_ms_per_step": f["ms"],
+                        "avg_launch_ms": f["ms"] / f["launches"],
+                        "executed_tflops": f["exec_flops"] / sec / 1e12, "executed_frac": f["exec_flops"] / sec / 1e12 / PEAK,
+                        "algorithmic_tflops": f["algo_flops"] / sec / 1e12,
+                        "algorithmic_frac": f["algo_flops"] / sec / 1e12 / PEAK_DEFAULT,
+                        "algorithmic_gflop_per_launch": f["algo_flops"] / f["launches"] / 1e9,
+                        "traffic": pj.get("hbm_bytes_per_launch_corrected"), "mfma_util_percent_pmc": pj.get("MfmaUtil_percent"),
+                        # the same family's weighted average launch in the committed rocprofv3 --kernel-trace --stats table
+                        # (profiles/rNN_kernel_stats_serial.txt, folded into the PMC summary of this library): compare with
+                        # avg_launch_ms * 1e3, which comes from HIP events inside this very run
+                        "rocprof_avg_us": pj.get("rocprof_avg_us")}
 
-        ent = fam_entry(dom)
-        if fam_fp32 is not None and fam_fp32[dom]["launches"]:
-            f0 = fam_fp32[dom]
-            ent["with_fp32_mfma_only"] = {"kernel_ms_per_step": f0["ms"], "executed_frac": f0["exec_flops"] / (f0["ms"] * 1e-3) / 1e12 / PEAK_DEFAULT,
-                                          "all_conv_ms_per_step": sum(f["ms"] for f in fam_fp32.values()),
-                                          "what": "the same kernel metered in steps whose 1x1 layers run on the fp32 MFMA (GLASS_PW_SPLIT=0): the "
-                                                  "split kernel's power draw costs every other kernel of the step clock"}
-        other = [fam_entry(k) for k in fam if k != dom and fam[k]["launches"]]
+            ent = fam_entry(dom)
+            if fam_fp32 is not None and fam_fp32[dom]["launches"]:
+                f0 = fam_fp32[dom]
+                ent["with_fp32_mfma_only"] = {"kernel_ms_per_step": f0["ms"], "executed_frac": f0["exec_flops"] / (f0["ms"] * 1e-3) / 1e12 / PEAK_DEFAULT,
+                                              "all_conv_ms_per_step": sum(f["ms"] for f in fam_fp32.values()),
+                                              "what": "the same kernel metered in steps whose 1x1 layers run on the fp32 MFMA (GLASS_PW_SPLIT=0): the "
+                                                      "split kernel's power draw costs every other kernel of the step clock"}
+            other = [fam_entry(k) for k in fam if k != dom and fam[k]["launches"]]
         line = {
             "metric": "images/sec/GPU end-to-end spotting, 1000x1000, ~32 RoIs; 1/2/4/8 GPU scaling",
             "value": value, "unit": "images/sec", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -789,55 +854,58 @@ def main():
             "comm": comm,
             "images_per_sec_per_gpu": value / world,
             "hbm_peak_reserved_gb": torch.cuda.max_memory_reserved(dev) / 1e9,   # rank 0, whole run (of 288 GB)
-            "roofline": {"bound": "mfma", "kernel": ent["kernel"],
-                         # `achieved` = the FLOP this kernel really issues to the matrix cores / its measured time, `frac` =
-                         # achieved / peak <= 1: the MFMA utilisation, to be compared with `mfma_util_percent_pmc` / 100
-                         # (SQ_VALU_MFMA_BUSY_CYCLES of the same kernel family).  The Winograd kernels issue 4x (F(4x4,3x3))
-                         # / 2.25x (F(2x2,3x3)) fewer multiplies than the direct-convolution count SURVEY 8d prices a layer
-                         # at; that ALGORITHMIC rate is reported next to it (`algorithmic_tflops`, `algorithmic_frac` - may
-                         # exceed 1 - and `algorithmic_speedup_vs_direct` = algorithmic / executed FLOP).
-                         "achieved": ent["executed_tflops"], "peak": PEAK, "unit": "TFLOP/s",
-                         "frac": ent["executed_frac"],
-                         "peak_sustained_measured": FP32_MFMA_SUSTAINED_TFLOPS if args.precision == "fp32" else None,
-                         "frac_of_sustained_peak": (ent["executed_tflops"] / FP32_MFMA_SUSTAINED_TFLOPS) if args.precision == "fp32" else None,
-                         "achieved_is": "executed MFMA FLOP / kernel time (utilisation); the direct-convolution (algorithmic) rate is in algorithmic_*",
-                         "algorithmic_tflops": ent["algorithmic_tflops"], "algorithmic_frac": ent["algorithmic_frac"],
-                         "algorithmic_speedup_vs_direct": ent["algorithmic_tflops"] / ent["executed_tflops"],
-                         "executed_tflops": ent["executed_tflops"], "executed_frac": ent["executed_frac"],
-                         "traffic": ent["traffic"],
-                         "traffic_note": pmc_note,
-                         # the HBM side of the same kernel: PMC bytes per launch / its average launch time, against the 8 TB/s
-                         # nominal peak (MI355X_MICROARCH.md; ~6.3 TB/s is what a streaming kernel sustains) - with `frac` this
-                         # says which roofline, if any, binds: both well below 1 = issue / latency / power-bound
-                         "hbm_tbps": (ent["traffic"] / (ent["avg_launch_ms"] * 1e-3) / 1e12) if ent["traffic"] else None,
-                         "hbm_frac_of_peak": (ent["traffic"] / (ent["avg_launch_ms"] * 1e-3) / 8e12) if ent["traffic"] else None,
-                         "mfma_util_percent_pmc": ent["mfma_util_percent_pmc"],
-                         "launches_per_step": ent["launches_per_step"],
-                         "algorithmic_gflop_per_launch": ent["algorithmic_gflop_per_launch"],
-                         "avg_launch_ms": ent["avg_launch_ms"], "rocprof_avg_us": ent["rocprof_avg_us"],
-                         "kernel_ms_per_step": ent["kernel_ms_per_step"],
-                         "share_of_step": ent["kernel_ms_per_step"] / ms_per_step,
-                         "frac_with_fp32_mfma_only": (ent.get("with_fp32_mfma_only") or {}).get("executed_frac"),
-                         "with_fp32_mfma_only": ent.get("with_fp32_mfma_only"),
-                         "other_mfma_kernels": other,
-                         "all_conv_launches_per_step": n_launch, "all_conv_ms_per_step": conv_ms,
-                         "all_conv_algorithmic_tflops": conv_flops / (conv_ms * 1e-3) / 1e12},
-            "whole_step_tflops": conv_flops / (ms_per_step * 1e-3) / 1e12,
-            # north star: throughput "as fraction of the conv-bound roofline" = fp32 MFMA peak / direct-conv FLOPs per
-            # image (0.846 TFLOP at 1024^2, P=100, R=32 -> 186 img/s/GPU); the convs of this very step,
-            # counted the same way, give the per-image figure used here.  > 1 is possible only because the 3x3 layers
-            # run Winograd (2.25x fewer multiplies than the direct-convolution count).
-            "conv_bound_roofline": {"tflop_per_image": conv_flops / B / 1e12,
-                                    "images_per_sec_per_gpu": FP32_MFMA_PEAK_TFLOPS / (conv_flops / B / 1e12),
-                                    "frac": (value / world) / (FP32_MFMA_PEAK_TFLOPS / (conv_flops / B / 1e12)),
-                                    # the REFERENCE's direct-convolution count for this configuration (422.9 GMAC =
-                                    # 0.846 TFLOP per image at 1024^2, P = 100, R = 32 -> 186 images/s/GPU): the step above
-                                    # issues fewer convolution FLOP than that where it restructures exactly (P2P3 fusion on
-                                    # the pooled bins instead of the whole map), so this is the fixed yardstick across rounds
-                                    "survey_tflop_per_image": SURVEY_TFLOP_PER_IMAGE if (args.side, args.rois, args.workload) == (SIDE, ROIS, "e2e") else None,
-                                    "frac_vs_survey": ((value / world) / (FP32_MFMA_PEAK_TFLOPS / SURVEY_TFLOP_PER_IMAGE))
-                                    if (args.side, args.rois, args.workload) == (SIDE, ROIS, "e2e") else None},
         }
+        if args.full:
+            line.update({
+                "roofline": {"bound": "mfma", "kernel": ent["kernel"],
+                             # `achieved` = the FLOP this kernel really issues to the matrix cores / its measured time, `frac` =
+                             # achieved / peak <= 1: the MFMA utilisation, to be compared with `mfma_util_percent_pmc` / 100
+                             # (SQ_VALU_MFMA_BUSY_CYCLES of the same kernel family).  The Winograd kernels issue 4x (F(4x4,3x3))
+                             # / 2.25x (F(2x2,3x3)) fewer multiplies than the direct-convolution count SURVEY 8d prices a layer
+                             # at; that ALGORITHMIC rate is reported next to it (`algorithmic_tflops`, `algorithmic_frac` - may
+                             # exceed 1 - and `algorithmic_speedup_vs_direct` = algorithmic / executed FLOP).
+                             "achieved": ent["executed_tflops"], "peak": PEAK, "unit": "TFLOP/s",
+                             "frac": ent["executed_frac"],
+                             "peak_sustained_measured": FP32_MFMA_SUSTAINED_TFLOPS if args.precision == "fp32" else None,
+                             "frac_of_sustained_peak": (ent["executed_tflops"] / FP32_MFMA_SUSTAINED_TFLOPS) if args.precision == "fp32" else None,
+                             "achieved_is": "executed MFMA FLOP / kernel time (utilisation); the direct-convolution (algorithmic) rate is in algorithmic_*",
+                             "algorithmic_tflops": ent["algorithmic_tflops"], "algorithmic_frac": ent["algorithmic_frac"],
+                             "algorithmic_speedup_vs_direct": ent["algorithmic_tflops"] / ent["executed_tflops"],
+                             "executed_tflops": ent["executed_tflops"], "executed_frac": ent["executed_frac"],
+                             "traffic": ent["traffic"],
+                             "traffic_note": pmc_note,
+                             # the HBM side of the same kernel: PMC bytes per launch / its average launch time, against the 8 TB/s
+                             # nominal peak (MI355X_MICROARCH.md; ~6.3 TB/s is what a streaming kernel sustains) - with `frac` this
+                             # says which roofline, if any, binds: both well below 1 = issue / latency / power-bound
+                             "hbm_tbps": (ent["traffic"] / (ent["avg_launch_ms"] * 1e-3) / 1e12) if ent["traffic"] else None,
+                             "hbm_frac_of_peak": (ent["traffic"] / (ent["avg_launch_ms"] * 1e-3) / 8e12) if ent["traffic"] else None,
+                             "mfma_util_percent_pmc": ent["mfma_util_percent_pmc"],
+                             "launches_per_step": ent["launches_per_step"],
+                             "algorithmic_gflop_per_launch": ent["algorithmic_gflop_per_launch"],
+                             "avg_launch_ms": ent["avg_launch_ms"], "rocprof_avg_us": ent["rocprof_avg_us"],
+                             "kernel_ms_per_step": ent["kernel_ms_per_step"],
+                             "share_of_step": ent["kernel_ms_per_step"] / ms_per_step,
+                             "frac_with_fp32_mfma_only": (ent.get("with_fp32_mfma_only") or {}).get("executed_frac"),
+                             "with_fp32_mfma_only": ent.get("with_fp32_mfma_only"),
+                             "other_mfma_kernels": other,
+                             "all_conv_launches_per_step": n_launch, "all_conv_ms_per_step": conv_ms,
+                             "all_conv_algorithmic_tflops": conv_flops / (conv_ms * 1e-3) / 1e12},
+                "whole_step_tflops": conv_flops / (ms_per_step * 1e-3) / 1e12,
+                # north star: throughput "as fraction of the conv-bound roofline" = fp32 MFMA peak / direct-conv FLOPs per
+                # image (0.846 TFLOP at 1024^2, P=100, R=32 -> 186 img/s/GPU); the convs of this very step,
+                # counted the same way, give the per-image figure used here.  > 1 is possible only because the 3x3 layers
+                # run Winograd (2.25x fewer multiplies than the direct-convolution count).
+                "conv_bound_roofline": {"tflop_per_image": conv_flops / B / 1e12,
+                                        "images_per_sec_per_gpu": FP32_MFMA_PEAK_TFLOPS / (conv_flops / B / 1e12),
+                                        "frac": (value / world) / (FP32_MFMA_PEAK_TFLOPS / (conv_flops / B / 1e12)),
+                                        # the REFERENCE's direct-convolution count for this configuration (422.9 GMAC =
+                                        # 0.846 TFLOP per image at 1024^2, P = 100, R = 32 -> 186 images/s/GPU): the step above
+                                        # issues fewer convolution FLOP than that where it restructures exactly (P2P3 fusion on
+                                        # the pooled bins instead of the whole map), so this is the fixed yardstick across rounds
+                                        "survey_tflop_per_image": SURVEY_TFLOP_PER_IMAGE if (args.side, args.rois, args.workload) == (SIDE, ROIS, "e2e") else None,
+                                        "frac_vs_survey": ((value / world) / (FP32_MFMA_PEAK_TFLOPS / SURVEY_TFLOP_PER_IMAGE))
+                                        if (args.side, args.rois, args.workload) == (SIDE, ROIS, "e2e") else None},
+            })
         line.update(extras)
         if args.precision == "fp32":
             line["arithmetic"] = ("fp32 operands, exact fp32 products, fp32 accumulation everywhere.  Convolutions on v_mfma_f32_16x16x4 / "
@@ -868,7 +936,7 @@ def main():
         if args.runner_policy:
             line["config"]["inputs"] = (f"--runner-policy: uint8 HWC host images, resized x{policy_ratio:g} to {policy_side}x{policy_side} by the "
                                         "runner's policy: PCIe-inclusive and a LARGER workload than the metric's, NOT the contract's value")
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(cfg, sd, args.cpu_side, args.rois)
         elif world > 1:
             # the CPU baseline is timed on rank 0 of the N = 1 run only (it needs the host cores to itself); an N > 1 line

@@ -312,8 +312,9 @@ def test_config4_fp16_conv_mode_tracks_the_fp32_path(sd):
     assert np.abs(p - q).mean() < 5e-3
 
 
-def _compare_reduced(det, n, ref, what):
-    """fp16 modes: proposals and detections matched as SETS (order / thresholds move under fp16 noise)"""
+def _compare_reduced(det, n, ref, what, det_ref=None):
+    """fp16 modes: proposals and detections matched as SETS (order / thresholds move under fp16 noise).  `det_ref`: the oracle's
+    detections of the PRODUCT's proposals (teacher-forced box head), held to tighter bounds in place of ref's detections"""
     from parity import match_box_sets
     pb, pl, pc = det.proposals
     c = int(pc[n])
@@ -322,6 +323,15 @@ def _compare_reduced(det, n, ref, what):
     assert fr >= 0.98 and fg >= 0.98 and ds < 0.06 and db < 1.0       # measured: >= 0.99 matched, dlogit <= 4.1e-2, dbox <= 0.51 px
     d = det.detected if det.detected is not None else det
     k = d.counts_host[n]
+    if det_ref is not None:
+        fr, fg, ds, db = match_box_sets(d.boxes[n, :k].cpu().numpy(), d.scores[n, :k].cpu().numpy(), det_ref["pred_boxes"].numpy(),
+                                        det_ref["scores"].numpy())
+        print(f"[parity] {what}: detections {k} vs oracle box head on the product's proposals {len(det_ref['scores'])}: matched "
+              f"{fr:.3f} / {fg:.3f}, max |dscore| {ds:.3e}, max |dbox| {db:.3e}")
+        # measured (fp16 / fp16s, the oracle on AVX-512, AVX2 and SSE4.1 code paths, 1 or 16 threads): all but at most ONE of 18-22
+        # matched, dscore <= 4.7e-3, dbox <= 0.19 px
+        assert fr >= 0.94 and fg >= 0.94 and ds < 0.02 and db < 0.5
+        return
     fr, fg, ds, db = match_box_sets(d.boxes[n, :k].cpu().numpy(), d.scores[n, :k].cpu().numpy(), ref["pred_boxes"].numpy(), ref["scores"].numpy())
     print(f"[parity] {what}: detections {k} vs oracle {len(ref['scores'])}: matched {fr:.3f} / {fg:.3f}, max |dscore| {ds:.3e}, max |dbox| {db:.3e}")
     # (a detection is scored on ITS proposal, which moved by up to db pixels: the score bound is the proposal logits' bound;
@@ -349,6 +359,16 @@ def test_fp16_modes_match_their_emulating_oracle_small(sd, prec):
         ref = O.glass_inference(sd, imgs, cfg, injected_boxes=boxes)
     res = m.inference([{"image": im.cuda()} for im in imgs], do_postprocess=False, override_boxes=[b.cuda() for b in boxes])
     det = res.batch
+    # detections teacher-forced: the oracle's box head on the product's OWN proposals.  Free-running, a proposal that moved by a
+    # fraction of a pixel re-samples its RoI, and which boxes then land inside the match tolerance follows the fp32 summation order
+    # torch's CPU backend picks for the host (the same product build: 17 of 19 detections of image 1 matched against the oracle
+    # on an AVX-512 host, 18 on an AVX2 one).  The proposals themselves are still compared free-running (_compare_reduced).
+    pb, _, pc = det.proposals
+    props = [pb[n, :int(pc[n])].cpu() for n in range(len(imgs))]
+    with O.emulate(prec), torch.no_grad():
+        x, hw = O.preprocess(imgs, cfg.MODEL.PIXEL_MEAN, cfg.MODEL.PIXEL_STD, 32)
+        sc, dl, og, _ = O.box_head_logits(sd, O.resnet50_fpn(sd, x), props, cfg)
+        tf_dets = O.box_inference(sc, dl, og, props, hw, cfg)
     # every step of every RoI: the product's decoder fed the emulating oracle's symbols (no near-tie cut)
     flat = torch.cat(boxes).contiguous().cuda()
     ri = torch.tensor([0] * 6 + [1] * 6, dtype=torch.int32, device="cuda:0")
@@ -359,7 +379,7 @@ def test_fp16_modes_match_their_emulating_oracle_small(sd, prec):
     # measured (round 6, 312 live steps): fp16 max 2.9e-3 / mean 9.1e-6 / agreement 1.0; fp16s 2.3e-3 / 1.3e-5 / 1.0
     assert mx < 6e-3 and mean < 5e-5 and agree > 0.99
     for n, r in enumerate(ref):
-        _compare_reduced(det, n, r, f"{prec} image {n}")
+        _compare_reduced(det, n, r, f"{prec} image {n}", det_ref=tf_dets[n])
         # free-running greedy decoding under fp16 noise: steps whose top-2 gap is below 1e-2 may legitimately pick the other
         # character; RoIs are compared up to their first such step, and the share of RoIs that have one is the ORACLE's own
         # property (random weights give flat distributions), asserted at what the oracle says instead of a blanket 1.0
