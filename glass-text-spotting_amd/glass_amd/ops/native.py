@@ -9,8 +9,9 @@ import collections
 import ctypes
 import math
 import os
+import struct
 import threading
-from typing import List, Optional, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -306,20 +307,24 @@ def winograd_pack(w: torch.Tensor, f43=False) -> torch.Tensor:
     return u
 
 
+def _wino_workgroups(m: int, N: int, H: int, W: int, Cout: int, wide: bool, body: bool = False) -> int:
+    """workgroups of a Winograd F(m x m, 3x3) launch (m = 4 | 2): wide 16 (F(4x4)) / 32 (F(2x2)) tiles x 128 channels per
+    workgroup, narrow twice the tiles x 64 channels; `body`: the full tile columns only (the last one runs as a strip)"""
+    tiles = N * ((H + m - 1) // m) * (W // m if body else (W + m - 1) // m)
+    per = (16 if m == 4 else 32) * (1 if wide else 2)
+    return -(-tiles // per) * (Cout // 128 if wide else Cout // 64)
+
+
 def _use_f43(N: int, H: int, W: int, Cout: int, Cin: int, body: bool = False) -> bool:
     """F(4x4,3x3) pays when the 4x4 tiling does not waste much of the map (H, W rounded up to multiples of 4 vs 2)
     and the grid still fills the chip (16 tiles x 128 channels per workgroup; 32 x 64 for the narrow shape).  `body`: only the
     full tile columns run on this kernel (width 4 k + 1: the last column is a strip convolution)."""
     t4 = ((H + 3) // 4) * (W // 4 if body else (W + 3) // 4)
     waste = (t4 * 16.0) / (((H + 1) // 2) * ((W + 1) // 2) * 4.0)
-    wide = Cout % 128 == 0 and Cin % 32 == 0
-    blocks = ((N * t4 + 15) // 16) * (Cout // 128) if wide else ((N * t4 + 31) // 32) * (Cout // 64)
-    return waste <= 1.25 and blocks >= 192
+    return waste <= 1.25 and _wino_workgroups(4, N, H, W, Cout, Cout % 128 == 0 and Cin % 32 == 0, body) >= 192
 
 
 NUM_CUS = 256
-_F43_SPLITK = os.environ.get("GLASS_F43_SPLITK", "1") != "0"        # (A/B switch of the F(4x4) split-K routing, read once)
-_SPLIT_LONGK = os.environ.get("GLASS_SPLIT_LONGK", "1") != "0"      # (A/B switch of _use_split's long-k rule, read once)
 
 
 def _use_split(px: int, Cin: int, Cout: int) -> bool:
@@ -328,7 +333,7 @@ def _use_split(px: int, Cin: int, Cout: int) -> bool:
     is 0.036 -> 0.050 ms) and, for the two-k-tile layers (Cin 64: prologue + epilogue per block are most of its life), only on big
     maps (64 -> 256 + residual: 0.93x at 8 x 256 x 256, 1.10x at 1 x 256 x 256) - profiles/r05_pw_split.txt, per-layer tables"""
     blocks = -(-px // 64) * (Cout // 128)
-    if _SPLIT_LONGK and 192 <= blocks < 384 and Cin >= 512:
+    if 192 <= blocks < 384 and Cin >= 512:
         # round 6: layers that fill the chip only 0.75 - 1.5 times but run a LONG k-loop per block (>= 16 k-tiles: the weight stream of a
         # block is amortised over its own k-loop, not over many blocks) - the box head's fc1 / fc2 at 800 rows, the FPN lateral on res5,
         # the recurrent layers' input projections: 13 - 25 % faster than the implicit-GEMM kernel (scripts/exp_fc1_split.py)
@@ -347,23 +352,16 @@ def _small_grid_3x3(N: int, H: int, W: int, Cout: int, Cin: int, can_body: bool,
     def rounds(blocks):
         return -(-blocks // NUM_CUS)
     cands = []
-    wide43 = Cout % 128 == 0 and Cin % 32 == 0
-    wide22 = Cout % 128 == 0 and Cin % 32 == 0
+    wide = Cout % 128 == 0 and Cin % 32 == 0
     for body in ((False, True) if can_body else (False,)):
         strip = 20.0 if body else 0.0
         if f43_ok and (not body or W % 4 == 1):
-            t4 = N * ((H + 3) // 4) * (W // 4 if body else (W + 3) // 4)
-            blocks = -(-t4 // 16) * (Cout // 128) if wide43 else -(-t4 // 32) * (Cout // 64)
-            cands.append((rounds(blocks) * ((10 + 0.34 * Cin) if wide43 else (9 + 0.56 * Cin)) + strip, "f43", body))
-        t2 = N * ((H + 1) // 2) * (W // 2 if body else (W + 1) // 2)
-        blocks = -(-t2 // 32) * (Cout // 128) if wide22 else -(-t2 // 64) * (Cout // 64)
-        cands.append((rounds(blocks) * ((9 + 0.30 * Cin) if wide22 else 3.0 * Cin) + strip, "f22", body))
+            blocks = _wino_workgroups(4, N, H, W, Cout, wide, body)
+            cands.append((rounds(blocks) * ((10 + 0.34 * Cin) if wide else (9 + 0.56 * Cin)) + strip, "f43", body))
+        blocks = _wino_workgroups(2, N, H, W, Cout, wide, body)
+        cands.append((rounds(blocks) * ((9 + 0.30 * Cin) if wide else 3.0 * Cin) + strip, "f22", body))
     t, kind, body = min(cands)
     return kind, body, t
-
-
-def _TLS_force_f43k():
-    return getattr(_TLS, "force_f43k", None)
 
 
 def _f43_splitk_plan(N: int, H: int, W: int, Cout: int, Cin: int, can_body: bool):
@@ -379,8 +377,7 @@ def _f43_splitk_plan(N: int, H: int, W: int, Cout: int, Cin: int, can_body: bool
     nk = Cin // 32
     best = None
     for body in ((False, True) if (can_body and W % 4 == 1) else (False,)):
-        t4 = N * ((H + 3) // 4) * (W // 4 if body else (W + 3) // 4)
-        blocks = -(-t4 // 16) * (Cout // 128)
+        blocks = _wino_workgroups(4, N, H, W, Cout, True, body)
         if blocks > NUM_CUS // 4:       # a quarter of the chip or less: with more, and two steps in flight, the other step's kernels
             continue                    # already fill the idle CUs and the split only adds a launch (8-image bench: 310.0 vs 309.0)
         for sl in (2, 3, 4, 6, 8, 12, 16, 24, 32):
@@ -522,18 +519,142 @@ def _packed(w, wt: torch.Tensor, kind) -> torch.Tensor:
     return winograd_pack(wt, kind)
 
 
+class ConvPlan(NamedTuple):
+    """One conv2d_nhwc launch: `entry` on weights `pack` (a ConvWeight pack kind; None: raw) with trailing int `flags` (None: none),
+    `splits` k-slices (0: none), then the last-column `strip` convolution; `cast`: x rounded to fp16 first; `path`: last_conv_path()"""
+    path: str
+    entry: str
+    pack: object = None
+    flags: Optional[int] = None
+    splits: int = 0
+    strip: bool = False
+    cast: bool = False
+
+
+_WORKSPACE_BYTES = {"glass_conv3x3_winograd43_splitk_nhwc": "glass_winograd43_splitk_workspace_bytes",
+                    "glass_conv2d_nhwc_splitk": "glass_conv2d_splitk_workspace_bytes"}
+_DESC_INTS = struct.Struct(f"{len(ConvDesc._fields_)}i")     # a ConvDesc as Python ints in one call (ctypes field reads are slow)
+
+
+def plan_conv(d: ConvDesc, rt: Routing, *, x_dtype: torch.dtype, out_dtype: torch.dtype, res_dtype: Optional[torch.dtype],
+              res_mode: int, packs, forced=None, f43k=None) -> ConvPlan:
+    """Which kernel conv2d_nhwc launches for layer `d` under `rt`: host arithmetic and host-only library queries, no tensors, nothing
+    cached.  res_dtype None: no residual; `res_mode`: the CALLER's (d.res_mode is 0 without one); `packs`: the ConvWeight's pack kinds
+    (None: raw); `forced` / `f43k`: conv2d_nhwc's `winograd` / `f43k`.  A forced kernel that cannot take `d` raises GlassLibraryError."""
+    L, dp = lib(), ctypes.byref(d)
+    N, H, W, Cin, Cout, KH, KW, sh, sw, _, _, Ho, Wo, ldx, _, _, y_cstride, _, _, _ = _DESC_INTS.unpack(d)
+    three = KH == 3 and KW == 3
+    half = (1 if x_dtype == torch.float16 else 0) | (2 if out_dtype == torch.float16 else 0) | (4 if res_dtype == torch.float16 else 0)
+    if half:
+        if rt.precision != "fp16s" or forced:
+            raise GlassLibraryError("float16 activation tensors need conv precision 'fp16s' (and no forced Winograd)")
+        # fp16 input, Cin / Cout multiples of 64: the kernel built for the fp16 matrix cores (csrc/conv_h16.hip, weights
+        # pre-rounded and packed once); everything else - fp32 entries, the 4/16/32-channel first layers, the narrow heads -
+        # stays on the fp32 template with fp16 operands
+        if rt.h16 and L.glass_conv_h16_supported(dp, half):
+            return ConvPlan("packed_fp16", "glass_conv2d_nhwc_h16_packed", "h16", half)
+        return ConvPlan("direct_fp16", "glass_conv2d_nhwc_h16", None, half)
+    if rt.precision in ("fp16", "fp16s") and not forced:
+        # fp32 tensors in an fp16 mode (every layer of 'fp16', the fp32-input layers of 'fp16s': fusion conv, fc1 / fc2): where
+        # a conv does enough work per input element, round the input to fp16 ONCE (glass_cast_f32_to_f16 - the rounding the
+        # template applies while staging) and run the fp16-MFMA kernel on it; fp32 output and residual as they are
+        if rt.h16 and KH * KW * Cout >= 512 and N * H * W * ldx > 0 and L.glass_conv_h16_supported(dp, 1):
+            return ConvPlan("packed_fp16", "glass_conv2d_nhwc_h16_packed", "h16", 1, cast=True)
+        return ConvPlan("direct_fp16", "glass_conv2d_nhwc_f16")
+    px = N * Ho * Wo
+    if forced in ("pws9", "pws6"):                   # forced: the exact-product bf16-split 1x1 kernel (tests, scripts)
+        if not L.glass_pointwise_split_supported(dp):
+            raise GlassLibraryError(f"winograd={forced!r} but glass_pointwise_split_supported() rejects this layer")
+        return ConvPlan("pointwise_split", "glass_conv1x1_pointwise_split_nhwc", "pws", int(forced[3]))
+    auto_1x1 = forced is None and KH == 1 and KW == 1
+    if (auto_1x1 and rt.split and _use_split(px, Cin, Cout) and L.glass_pointwise_split_supported(dp) and
+            (packs is None or "pws" in packs)):
+        return ConvPlan("pointwise_split", "glass_conv1x1_pointwise_split_nhwc", "pws", rt.split)
+    # the weight-streaming 1x1 kernel on the wide layers with long k-loops.  Layer by layer (scripts/bench_conv.py) it is
+    # ahead for every Cin >= 256 (256->1024 and 256->256 x1.08, 1024->256 x1.09, 512->128 x1.11, 512->2048 @32x32 x1.07;
+    # behind on 128->512 x0.92 and 64->256 x0.87), but routing the narrow / small ones to it (Cout 128, 8192-pixel maps)
+    # LOWERS the end-to-end rate: 274.1 images/s with this rule, 271 without the kernel, 267 with "Cin >= 256, >= 8192
+    # pixels" (three alternating runs each, same box).  Round 4: the res5-size layers with BOTH channel counts >= 512 (8192
+    # pixels at batch 8: 2048->512, 512->2048 +res, 1024->2048 s2, 1024->512 s2) are 7-13 % faster on it and worth +0.2 % end
+    # to end (five alternating runs: 280.3 vs 279.7); the Cout = 128 layers still are not (279.5), and below 8192 pixels the
+    # per-workgroup weight stream is not amortised (batch 2: 2-4x SLOWER than the direct kernel).
+    if (auto_1x1 and rt.pw and
+            (rt.pw == "all" or (Cin >= 256 and Cout >= 256 and px >= 16384) or (Cin >= 512 and Cout >= 512 and px >= 8192))
+            and L.glass_pointwise_supported(dp)):
+        return ConvPlan("pointwise", "glass_conv1x1_pointwise_nhwc", "pw")
+    use_wino = rt.winograd if forced is None else forced
+    if forced is None and use_wino and three:
+        # the Winograd kernel runs one 64-tile x 64-channel workgroup per CU: below ~96 workgroups (FPN p6, batch-2 res5)
+        # the direct kernel's smaller tiles fill the chip better (measured 0.68-0.82x vs 1.15x at 128 workgroups)
+        use_wino = ((N * ((H + 1) // 2) * ((W + 1) // 2) + 63) // 64) * (Cout // 64) >= 96
+    # odd widths (the local extractor's 16 x 33 maps): full tile columns on a Winograd kernel + the last pixel column as a strip
+    # convolution.  A model's layer takes the split only if its load prepared the strip weights - fold_conv(..., ragged=True) -
+    # so that no launch of the model path ever packs; raw tensors (tests, scripts) get them packed for the launch.
+    can_strip = (rt.ragged and three and W % 2 == 1 and W >= 5 and (2 * Cin) % 32 == 0 and y_cstride == 1 and ldx == Cin and
+                 res_mode in (0, 1) and N * H * W * ldx > 0 and (packs is None or "col1" in packs))
+    ragged = can_body = can_strip and W % 4 == 1
+    f43 = forced == "f43" or (forced is None and rt.f43 and use_wino and three and _use_f43(N, H, W, Cout, Cin, ragged))
+    f22_body = forced == "f22r"                     # forced: F(2x2) on the full tile columns + the last-column strip (tests)
+    if f22_body and not can_strip:
+        raise GlassLibraryError("winograd='f22r' needs an odd width >= 5, dense input, unit channel stride and res_mode 0/1")
+    t_alt = None                                    # modelled time of the launch the layer takes otherwise (small grids only)
+    if forced is None and use_wino and not f43 and three and rt.small_grid and L.glass_winograd_supported(dp):
+        # the F(4x4) grid does not fill the chip (one image in flight): rounds x workgroup time decides
+        kind, body, t_alt = _small_grid_3x3(N, H, W, Cout, Cin, can_strip, rt.f43 and bool(L.glass_winograd43_supported(dp)))
+        f43, ragged, f22_body = kind == "f43", kind == "f43" and body, kind == "f22" and body
+    # round 6: the same layers - and the ones the rule above already sent to the implicit-GEMM kernel - as a SPLIT-K launch of the
+    # F(4x4) kernel when the model says it is >= 15 % faster than what they take otherwise
+    if (forced is None and rt.winograd and rt.f43 and rt.small_grid and rt.splitk and rt.precision == "fp32" and three and
+            sh == 1 and sw == 1 and out_dtype == torch.float32 and y_cstride == 1 and res_mode in (0, 1) and
+            not _use_f43(N, H, W, Cout, Cin, can_body) and (packs is None or True in packs)):
+        plan = _f43_splitk_plan(N, H, W, Cout, Cin, can_strip)
+        if f43k is not None:                        # forced: a slice count, or (slices, body); 0 = never
+            sl, body = f43k if isinstance(f43k, tuple) else (f43k, False)
+            plan, t_alt = ((int(sl), bool(body) and can_body, 0.0) if sl else None), None
+        if plan is not None:
+            sl, body, t_sk = plan
+            if t_alt is None and not use_wino:
+                t_alt = _splitk_slices(rt, px, KH * KW * Cin, Cin, Cout, want_time=True)[1]
+            if (t_alt is None or t_sk < (0.8 if body else 0.85) * t_alt) and L.glass_winograd43_splitk_supported(dp, sl):
+                return ConvPlan("winograd43k", "glass_conv3x3_winograd43_splitk_nhwc", True, int(body), sl, strip=body)
+    if use_wino and f43 and three and L.glass_winograd43_supported(dp):
+        if ragged:
+            # width 4 k + 1: the F(4x4) kernel on the k full tile columns - 32 instead of 36 tiles per 16 x 33 map, and e.g.
+            # 1024 instead of 1152 workgroups = 4 instead of 4.5 rounds on 256 CUs - and the last pixel column as a KH = 3,
+            # KW = 1 convolution over the last two input columns seen as 2*Cin channels (x, y and the residual re-viewed as
+            # [N,H,1,W*ld] rows with a channel offset; no copy)
+            return ConvPlan("winograd43r", "glass_conv3x3_winograd43_body_nhwc", True, strip=True)
+        return ConvPlan("winograd43", "glass_conv3x3_winograd43_nhwc", True)
+    if forced == "f43":
+        raise GlassLibraryError("winograd='f43' but glass_winograd43_supported() rejects this layer")
+    if use_wino and three and L.glass_winograd_supported(dp):
+        path = "winograd128" if L.glass_winograd_block_channels(Cout, Cin) == 128 else "winograd"
+        if f22_body:
+            return ConvPlan(path + "r", "glass_conv3x3_winograd_body_nhwc", False, strip=True)
+        return ConvPlan(path, "glass_conv3x3_winograd_nhwc", False)
+    if forced:
+        raise GlassLibraryError("winograd=True but glass_winograd_supported() rejects this layer")
+    # few output pixels and a long K (one image in flight: box head fc layers, res4 / res5 3x3, the 11-row predictors): the
+    # k-tiles as `splits` independent slices of workgroups, partial sums through a workspace, ordered reduction
+    splits = _splitk_slices(rt, px, KH * KW * Cin, Cin, Cout) if (res_mode in (0, 1) or res_dtype is None) else 0
+    if splits > 1 and out_dtype == torch.float32 and L.glass_conv2d_splitk_supported(dp, splits):
+        return ConvPlan("direct", "glass_conv2d_nhwc_splitk", splits=splits)
+    return ConvPlan("direct", "glass_conv2d_nhwc")
+
+
 def conv2d_nhwc(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, *, stride=1, padding=0,
                 relu: int = 0, residual: Optional[torch.Tensor] = None, res_mode: int = 0,
                 out: Optional[torch.Tensor] = None, out_coff: int = 0, out_cstride: int = 1,
                 cin: Optional[int] = None, winograd: Optional[bool] = None, out_dtype: Optional[torch.dtype] = None,
-                precision: Optional[str] = None, routing: Optional[Routing] = None) -> torch.Tensor:
+                precision: Optional[str] = None, routing: Optional[Routing] = None, f43k=None) -> torch.Tensor:
     """y = act(conv(x, w) + bias [+ residual]).  x [N,H,W,ldx] NHWC, w [Cout,KH,KW,Cin]: a ConvWeight (the model path: packed
     forms built at load) or a plain device tensor (packed per launch where the chosen kernel needs it).
     3x3/stride 1/pad 1 layers that glass_winograd_supported() accepts go through the Winograd kernel
     (winograd=None: follow the routing; True/False force F(2x2,3x3) on / off for this call, "f43" forces the F(4x4,3x3)
-    kernel, "f22r" F(2x2,3x3) on the full tile columns of an odd-width map + the last-column strip).  Which kernel runs is decided by `routing` (default: the Routing stamped on `w` at model load, else the
-    raw-tensor default) with `precision` overriding its precision for this call - nothing process-global is read for a
-    model's layers."""
+    kernel, "f22r" F(2x2,3x3) on the full tile columns of an odd-width map + the last-column strip).  `f43k`: F(4x4) split-K
+    slices (None: the cost model decides, 0: never, else slices or (slices, body)).  plan_conv decides under `routing` (default:
+    the Routing stamped on `w` at model load, else the raw-tensor default; `precision` overrides its precision for this call) -
+    nothing process-global is read for a model's layers."""
     wt = w.raw if isinstance(w, ConvWeight) else _f32c(w, "w")
     rt = routing if routing is not None else routing_of(w)
     if precision is not None and precision != rt.precision:
@@ -545,7 +666,7 @@ def conv2d_nhwc(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, *, stri
         raise GlassLibraryError(f"cin={cin} does not match weight Cin={Cin}")
     sh, sw = _pair(stride)
     ph, pw = _pair(padding)
-    Ho, Wo = conv_out_size(H, W, KH, KW, stride, padding)
+    Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
     if out is None:
         # the output follows the input's storage dtype unless told otherwise (fp16 tensors exist only in 'fp16s' mode)
         out = torch.empty((N, Ho, Wo, Cout), dtype=out_dtype or x.dtype, device=x.device)
@@ -564,152 +685,29 @@ def conv2d_nhwc(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, *, stri
                  res_mode if residual is not None else 0, residual.shape[-1] if residual is not None else 0)
     if residual is not None:
         _fhc(residual, "residual")
-    def launch(entry: str, path: str, xt: torch.Tensor, weights: torch.Tensor, flags: Optional[int] = None) -> torch.Tensor:
-        """one conv entry of the library: (desc, x, w | packed weights, bias, residual, y[, flags], stream)"""
-        _TLS.last_path = path
-        args = [ctypes.byref(d), c_void_p(_dev(xt, "x")), c_void_p(_dev(weights, "w")),
-                c_void_p(_dev(bias, "bias") if bias is not None else None),
-                c_void_p(_dev(residual, "residual") if residual is not None else None), c_void_p(_dev(out, "out"))]
-        if flags is not None:
-            args.append(int(flags))
-        check(getattr(lib(), entry)(*args, c_void_p(stream_handle())), entry)
-        return out
-
-    any_half = x.dtype == torch.float16 or out.dtype == torch.float16 or (residual is not None and residual.dtype == torch.float16)
-    if any_half:
-        if rt.precision != "fp16s" or winograd:
-            raise GlassLibraryError("float16 activation tensors need conv precision 'fp16s' (and no forced Winograd)")
-        flags = (1 if x.dtype == torch.float16 else 0) | (2 if out.dtype == torch.float16 else 0) | \
-                (4 if residual is not None and residual.dtype == torch.float16 else 0)
-        # fp16 input, Cin / Cout multiples of 64: the kernel built for the fp16 matrix cores (csrc/conv_h16.hip, weights
-        # pre-rounded and packed once); everything else - fp32 entries, the 4/16/32-channel first layers, the narrow heads -
-        # stays on the fp32 template with fp16 operands
-        if rt.h16 and lib().glass_conv_h16_supported(ctypes.byref(d), int(flags)):
-            return launch("glass_conv2d_nhwc_h16_packed", "packed_fp16", x, _packed(w, wt, "h16"), flags)
-        return launch("glass_conv2d_nhwc_h16", "direct_fp16", x, wt, flags)
-    if rt.precision in ("fp16", "fp16s") and not winograd:
-        # fp32 tensors in an fp16 mode (every layer of 'fp16', the fp32-input layers of 'fp16s': fusion conv, fc1 / fc2): where
-        # a conv does enough work per input element, round the input to fp16 ONCE (glass_cast_f32_to_f16 - the rounding the
-        # template applies while staging) and run the fp16-MFMA kernel on it; fp32 output and residual as they are
-        if (rt.h16 and KH * KW * Cout >= 512 and x.numel() > 0 and
-                lib().glass_conv_h16_supported(ctypes.byref(d), 1)):
-            xh = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-            check(lib().glass_cast_f32_to_f16(c_void_p(_dev(x, "x")), c_void_p(_dev(xh)), ctypes.c_int64(x.numel()),
-                                              c_void_p(stream_handle())), "glass_cast_f32_to_f16")
-            return launch("glass_conv2d_nhwc_h16_packed", "packed_fp16", xh, _packed(w, wt, "h16"), 1)
-        return launch("glass_conv2d_nhwc_f16", "direct_fp16", x, wt)
-    # the weight-streaming 1x1 kernel on the wide layers with long k-loops.  Layer by layer (scripts/bench_conv.py) it is
-    # ahead for every Cin >= 256 (256->1024 and 256->256 x1.08, 1024->256 x1.09, 512->128 x1.11, 512->2048 @32x32 x1.07;
-    # behind on 128->512 x0.92 and 64->256 x0.87), but routing the narrow / small ones to it (Cout 128, 8192-pixel maps)
-    # LOWERS the end-to-end rate: 274.1 images/s with this rule, 271 without the kernel, 267 with "Cin >= 256, >= 8192
-    # pixels" (three alternating runs each, same box).  Round 4: the res5-size layers with BOTH channel counts >= 512 (8192
-    # pixels at batch 8: 2048->512, 512->2048 +res, 1024->2048 s2, 1024->512 s2) are 7-13 % faster on it and worth +0.2 % end
-    # to end (five alternating runs: 280.3 vs 279.7); the Cout = 128 layers still are not (279.5), and below 8192 pixels the
-    # per-workgroup weight stream is not amortised (batch 2: 2-4x SLOWER than the direct kernel).
-    px = N * Ho * Wo
-    if winograd in ("pws9", "pws6"):                 # forced: the exact-product bf16-split 1x1 kernel (tests, scripts)
-        if not lib().glass_pointwise_split_supported(ctypes.byref(d)):
-            raise GlassLibraryError(f"winograd={winograd!r} but glass_pointwise_split_supported() rejects this layer")
-        return launch("glass_conv1x1_pointwise_split_nhwc", "pointwise_split", x, _packed(w, wt, "pws"), int(winograd[3]))
-    if (winograd is None and rt.split and KH == 1 and KW == 1 and _use_split(px, Cin, Cout) and
-            lib().glass_pointwise_split_supported(ctypes.byref(d)) and (not isinstance(w, ConvWeight) or "pws" in w.packs)):
-        return launch("glass_conv1x1_pointwise_split_nhwc", "pointwise_split", x, _packed(w, wt, "pws"), rt.split)
-    if (winograd is None and rt.pw and KH == 1 and KW == 1 and
-            (rt.pw == "all" or (Cin >= 256 and Cout >= 256 and px >= 16384) or (Cin >= 512 and Cout >= 512 and px >= 8192))
-            and lib().glass_pointwise_supported(ctypes.byref(d))):
-        return launch("glass_conv1x1_pointwise_nhwc", "pointwise", x, _packed(w, wt, "pw"))
-    use_wino = rt.winograd if winograd is None else winograd
-    if winograd is None and use_wino and KH == 3:
-        # the Winograd kernel runs one 64-tile x 64-channel workgroup per CU: below ~96 workgroups (FPN p6, batch-2 res5)
-        # the direct kernel's smaller tiles fill the chip better (measured 0.68-0.82x vs 1.15x at 128 workgroups)
-        use_wino = ((N * ((H + 1) // 2) * ((W + 1) // 2) + 63) // 64) * (Cout // 64) >= 96
-    # (a model's layer takes the split only if its load prepared the strip weights - fold_conv(..., ragged=True) - so that no
-    #  launch of the model path ever packs; raw tensors (tests, scripts) get them packed for the launch)
-    # odd widths (the local extractor's 16 x 33 maps): full tile columns on a Winograd kernel + the last pixel column as a strip
-    # convolution.  A model's layer takes the split only if its load prepared the strip weights - fold_conv(..., ragged=True) -
-    # so that no launch of the model path ever packs; raw tensors (tests, scripts) get them packed for the launch.
-    strip_ok = (rt.ragged and KH == 3 and KW == 3 and W % 2 == 1 and W >= 5 and (2 * Cin) % 32 == 0 and out_cstride == 1 and
-                ldx == Cin and res_mode in (0, 1) and x.numel() > 0 and (not isinstance(w, ConvWeight) or "col1" in w.packs))
-    ragged = strip_ok and W % 4 == 1
-    f43 = winograd == "f43" or (winograd is None and rt.f43 and use_wino and KH == 3 and _use_f43(N, H, W, Cout, Cin, ragged))
-    f22_body = False
-    t_alt = None                                    # modelled time of the launch the layer takes otherwise (small grids only)
-    if winograd == "f22r":                          # forced: F(2x2) on the full tile columns + the last-column strip (tests)
-        if not strip_ok:
-            raise GlassLibraryError("winograd='f22r' needs an odd width >= 5, dense input, unit channel stride and res_mode 0/1")
-        f22_body = True
-    if (winograd is None and use_wino and not f43 and KH == 3 and KW == 3 and rt.small_grid and
-            lib().glass_winograd_supported(ctypes.byref(d))):
-        # the F(4x4) grid does not fill the chip (one image in flight): rounds x workgroup time decides
-        kind, body, t_alt = _small_grid_3x3(N, H, W, Cout, Cin, strip_ok,
-                                            rt.f43 and bool(lib().glass_winograd43_supported(ctypes.byref(d))))
-        f43, ragged, f22_body = kind == "f43", kind == "f43" and body, kind == "f22" and body
-    # round 6: the same layers - and the ones the rule above already sent to the implicit-GEMM kernel - as a SPLIT-K launch of the
-    # F(4x4) kernel when the model says it is >= 15 % faster than what they take otherwise
-    if (_F43_SPLITK and winograd is None and rt.winograd and rt.f43 and rt.small_grid and rt.splitk and rt.precision == "fp32" and KH == 3 and KW == 3 and
-            _pair(stride) == (1, 1) and x.dtype == torch.float32 and out.dtype == torch.float32 and out_cstride == 1 and res_mode in (0, 1) and
-            not _use_f43(N, H, W, Cout, Cin, strip_ok and W % 4 == 1) and (not isinstance(w, ConvWeight) or True in w.packs)):
-        plan = _f43_splitk_plan(N, H, W, Cout, Cin, strip_ok and (not isinstance(w, ConvWeight) or "col1" in w.packs))
-        if _TLS_force_f43k() is not None:           # (scripts/exp_f43_splitk.py: force a slice count to fit the model; 0 = never)
-            fs = _TLS_force_f43k()                  # slices, or (slices, body)
-            fs = fs if isinstance(fs, tuple) else (fs, False)
-            plan, t_alt = ((int(fs[0]), bool(fs[1]) and strip_ok and W % 4 == 1, 0.0) if fs[0] else None), None
-        if plan is not None:
-            sl, body, t_sk = plan
-            if t_alt is None:
-                t_alt = _splitk_slices(rt, N * Ho * Wo, KH * KW * Cin, Cin, Cout, want_time=True)[1] if not use_wino else None
-            if (t_alt is None or t_sk < (0.8 if body else 0.85) * t_alt) and lib().glass_winograd43_splitk_supported(ctypes.byref(d), sl):
-                nbytes = int(lib().glass_winograd43_splitk_workspace_bytes(ctypes.byref(d), sl))
-                ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-                check(lib().glass_conv3x3_winograd43_splitk_nhwc(
-                    ctypes.byref(d), c_void_p(_dev(x, "x")), c_void_p(_dev(_packed(w, wt, True), "w")),
-                    c_void_p(_dev(bias, "bias") if bias is not None else None),
-                    c_void_p(_dev(residual, "residual") if residual is not None else None), c_void_p(_dev(out, "out")), int(sl), int(body),
-                    c_void_p(_dev(ws)), ctypes.c_int64(nbytes), c_void_p(stream_handle())), "glass_conv3x3_winograd43_splitk_nhwc")
-                if body:
-                    _last_column_strip(x, _packed(w, wt, "col1"), bias, residual, out, d, out_coff)
-                _TLS.last_path = "winograd43k"        # (bench / profiling: F(4x4) split-K + reduction)
-                return out
-    if use_wino and f43 and KH == 3 and KW == 3 and lib().glass_winograd43_supported(ctypes.byref(d)):
-        if ragged:
-            # width 4 k + 1: the F(4x4) kernel on the k full tile columns - 32 instead of 36 tiles per 16 x 33 map, and e.g.
-            # 1024 instead of 1152 workgroups = 4 instead of 4.5 rounds on 256 CUs - and the last pixel column as a KH = 3,
-            # KW = 1 convolution over the last two input columns seen as 2*Cin channels (x, y and the residual re-viewed as
-            # [N,H,1,W*ld] rows with a channel offset; no copy)
-            launch("glass_conv3x3_winograd43_body_nhwc", "winograd43", x, _packed(w, wt, True))
-            _last_column_strip(x, _packed(w, wt, "col1"), bias, residual, out, d, out_coff)
-            _TLS.last_path = "winograd43r"          # (bench / profiling: F(4x4) body + last-column strip)
-            return out
-        return launch("glass_conv3x3_winograd43_nhwc", "winograd43", x, _packed(w, wt, True))
-    if winograd == "f43":
-        raise GlassLibraryError("winograd='f43' but glass_winograd43_supported() rejects this layer")
-    if use_wino and KH == 3 and KW == 3 and lib().glass_winograd_supported(ctypes.byref(d)):
-        path = "winograd128" if lib().glass_winograd_block_channels(Cout, Cin) == 128 else "winograd"
-        if f22_body:
-            launch("glass_conv3x3_winograd_body_nhwc", path, x, _packed(w, wt, False))
-            _last_column_strip(x, _packed(w, wt, "col1"), bias, residual, out, d, out_coff)
-            _TLS.last_path = path + "r"             # (F(2x2) body + last-column strip)
-            return out
-        return launch("glass_conv3x3_winograd_nhwc", path, x, _packed(w, wt, False))
-    if winograd:
-        raise GlassLibraryError("winograd=True but glass_winograd_supported() rejects this layer")
-    splits = _splitk_slices(rt, N * Ho * Wo, KH * KW * Cin, Cin, Cout) if (res_mode in (0, 1) or residual is None) else 0
-    if splits > 1 and out.dtype == torch.float32 and x.dtype == torch.float32 and lib().glass_conv2d_splitk_supported(ctypes.byref(d), splits):
-        # few output pixels and a long K (one image in flight: box head fc layers, res4 / res5 3x3, the 11-row predictors):
-        # the k-tiles as `splits` independent slices of workgroups, partial sums through a workspace, ordered reduction
-        nbytes = int(lib().glass_conv2d_splitk_workspace_bytes(ctypes.byref(d), splits))
+    path, entry, pack, flags, splits, strip, cast = plan_conv(
+        d, rt, x_dtype=x.dtype, out_dtype=out.dtype, res_dtype=residual.dtype if residual is not None else None, res_mode=res_mode,
+        packs=w.packs if isinstance(w, ConvWeight) else None, forced=winograd, f43k=f43k)
+    _TLS.last_path = path
+    L = lib()
+    xt = x
+    if cast:
+        xt = torch.empty(x.shape, dtype=torch.float16, device=x.device)
+        check(L.glass_cast_f32_to_f16(c_void_p(_dev(x, "x")), c_void_p(_dev(xt)), ctypes.c_int64(x.numel()),
+                                      c_void_p(stream_handle())), "glass_cast_f32_to_f16")
+    # every conv entry: (desc, x, w | packed weights, bias, residual, y[, splits][, flags][, workspace, bytes], stream)
+    args = [ctypes.byref(d), c_void_p(_dev(xt, "x")), c_void_p(_dev(wt if pack is None else _packed(w, wt, pack), "w")),
+            c_void_p(_dev(bias, "bias") if bias is not None else None),
+            c_void_p(_dev(residual, "residual") if residual is not None else None), c_void_p(_dev(out, "out"))]
+    tail = [] if flags is None else [flags]
+    if splits:
+        nbytes = int(getattr(L, _WORKSPACE_BYTES[entry])(ctypes.byref(d), splits))
         ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        _TLS.last_path = "direct"
-        check(lib().glass_conv2d_nhwc_splitk(ctypes.byref(d), c_void_p(_dev(x, "x")), c_void_p(_dev(wt, "w")),
-                                             c_void_p(_dev(bias, "bias") if bias is not None else None),
-                                             c_void_p(_dev(residual, "residual") if residual is not None else None),
-                                             c_void_p(_dev(out, "out")), splits, c_void_p(_dev(ws)), ctypes.c_int64(nbytes),
-                                             c_void_p(stream_handle())), "glass_conv2d_nhwc_splitk")
-        return out
-    return launch("glass_conv2d_nhwc", "direct", x, wt)
-
-
-_DUAL = os.environ.get("GLASS_PW_DUAL", "1") != "0"                # (A/B switch of the shortcut-into-conv3 fusion, read once)
+        tail = [splits] + tail + [c_void_p(_dev(ws)), ctypes.c_int64(nbytes)]
+    check(getattr(L, entry)(*args, *tail, c_void_p(stream_handle())), entry)
+    if strip:
+        _last_column_strip(x, _packed(w, wt, "col1"), bias, residual, out, d, out_coff)
+    return out
 
 
 def prepare_dual_weights(w1, w2) -> Optional["ConvWeight"]:
@@ -719,7 +717,7 @@ def prepare_dual_weights(w1, w2) -> Optional["ConvWeight"]:
     r1, r2 = _raw(w1), _raw(w2)
     load = getattr(_TLS, "load", None)
     rt = load if load is not None else _DEFAULT
-    if (not _DUAL or rt.precision != "fp32" or rt.split != 9 or not r1.is_cuda or r1.shape[1:3] != (1, 1) or r2.shape[1:3] != (1, 1) or
+    if (rt.precision != "fp32" or rt.split != 9 or not r1.is_cuda or r1.shape[1:3] != (1, 1) or r2.shape[1:3] != (1, 1) or
             r1.shape[0] != r2.shape[0] or r1.shape[0] % 128 or r1.shape[3] % 32 or r2.shape[3] % 32):
         return None
     cw = ConvWeight(torch.cat([r1, r2], dim=3).contiguous(), routing=load)
@@ -804,12 +802,13 @@ def _splitk_slices(rt: Routing, M: int, Ktot: int, Cin: int, Cout: int, want_tim
         wpc = max(1.0, tiles * s / NUM_CUS)
         extra = 0.0 if s == 1 else 2.0 * s * M * Cout * 4 / 4e6 + 5.0 + 0.3 * s
         return nk / s * (0.75 if wpc <= 1.0 else 0.3 + 0.45 * wpc) + extra
-    best, tbest = 0, 0.85 * t(1)
+    t1 = t(1)
+    best, tbest = 0, 0.85 * t1
     for s in (2, 3, 4, 6, 7, 8, 9, 12, 14, 16, 18, 24, 28, 32):
-        if nk % s == 0 and nk // s >= 4 and t(s) < tbest:
-            best, tbest = s, t(s)
+        if nk % s == 0 and nk // s >= 4 and (ts := t(s)) < tbest:
+            best, tbest = s, ts
     if want_time:
-        return best, (tbest if best else t(1))
+        return best, (tbest if best else t1)
     return best
 
 

@@ -22,21 +22,20 @@ for name, N, H, W, Cin, Cout, res in SHAPES:
     w = K.prepare_conv_weights(torch.randn((Cout, 3, 3, Cin), device=dev) * 0.05, "all", ragged=(W % 4 == 1))
     b = torch.randn((Cout,), device=dev)
     r = torch.randn((N, H, W, Cout), device=dev) if res else None
-    f = lambda: K.conv2d_nhwc(x, w, b, padding=1, relu=1, residual=r, res_mode=1 if res else 0)
-    K._TLS.force_f43k = 0
-    y0 = f(); p0 = K.last_conv_path(); t0 = timeit(f)
+    f = lambda f43k=None: K.conv2d_nhwc(x, w, b, padding=1, relu=1, residual=r, res_mode=1 if res else 0, f43k=f43k)
+    f0 = lambda: f(0)
+    y0 = f0(); p0 = K.last_conv_path(); t0 = timeit(f0)
     row = [f"{name:30s} routed-without ({p0}) {t0:6.1f} us |"]
     for sl in (2, 4, 8, 16):
         if (Cin // 32) % sl:
             continue
-        K._TLS.force_f43k = sl
+        fs = lambda: f(sl)
         try:
-            y1 = f()
+            y1 = fs()
             assert K.last_conv_path() == "winograd43k", K.last_conv_path()
             err = float((y1 - y0).abs().max() / y0.abs().max())
-            row.append(f" s{sl}: {timeit(f):6.1f} us ({err:.1e})")
+            row.append(f" s{sl}: {timeit(fs):6.1f} us ({err:.1e})")
         except Exception as e:
             row.append(f" s{sl}: {str(e)[:40]}")
-    K._TLS.force_f43k = None
     f(); row.append(f" | model picks {K.last_conv_path()} {timeit(f):6.1f} us")
     print("".join(row), flush=True)

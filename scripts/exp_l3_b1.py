@@ -17,13 +17,12 @@ for res in (False, True):
     w = K.prepare_conv_weights(torch.randn((Cout, 3, 3, Cin), device=dev) * 0.05, "all", ragged=True)
     b = torch.randn((Cout,), device=dev)
     r = torch.randn((N, H, W, Cout), device=dev) if res else None
-    f = lambda: K.conv2d_nhwc(x, w, b, padding=1, relu=1, residual=r, res_mode=1 if res else 0)
-    K._TLS.force_f43k = 0
-    y0 = f(); print("routed", K.last_conv_path(), round(timeit(f), 1))
+    f = lambda f43k=None: K.conv2d_nhwc(x, w, b, padding=1, relu=1, residual=r, res_mode=1 if res else 0, f43k=f43k)
+    f0 = lambda: f(0)
+    y0 = f0(); print("routed", K.last_conv_path(), round(timeit(f0), 1))
     for fs in ((2, True), (4, True), (2, False)):
-        K._TLS.force_f43k = fs
-        y1 = f(); print(fs, K.last_conv_path(), round(timeit(f), 1), float((y1 - y0).abs().max() / y0.abs().max()))
-    K._TLS.force_f43k = None
+        f1 = lambda: f(fs)
+        y1 = f1(); print(fs, K.last_conv_path(), round(timeit(f1), 1), float((y1 - y0).abs().max() / y0.abs().max()))
     for wino in ("f43", "f22r", True):
         try:
             f2 = lambda: K.conv2d_nhwc(x, w, b, padding=1, relu=1, residual=r, res_mode=1 if res else 0, winograd=wino)

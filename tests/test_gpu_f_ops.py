@@ -315,19 +315,11 @@ def test_winograd43_splitk_matches_the_single_launch_and_torch(shape):
     kw = dict(padding=1, relu=1, residual=r, res_mode=1 if res else 0)
     out_a = torch.zeros((N, H, W, Cout + 8), device=dev)
     out_b = torch.zeros((N, H, W, Cout + 8), device=dev)
-    K._TLS.force_f43k = sl
-    try:
-        a = K.conv2d_nhwc(x, w, b, out=out_a, out_coff=4, **kw)
-        assert K.last_conv_path() == "winograd43k"
-        a2 = K.conv2d_nhwc(x, w, b, **kw)
-        a3 = K.conv2d_nhwc(x, w, b, **kw)
-    finally:
-        K._TLS.force_f43k = None
-    K._TLS.force_f43k = 0
-    try:
-        u = K.conv2d_nhwc(x, w, b, winograd="f43", out=out_b, out_coff=4, **kw)
-    finally:
-        K._TLS.force_f43k = None
+    a = K.conv2d_nhwc(x, w, b, out=out_a, out_coff=4, f43k=sl, **kw)
+    assert K.last_conv_path() == "winograd43k"
+    a2 = K.conv2d_nhwc(x, w, b, f43k=sl, **kw)
+    a3 = K.conv2d_nhwc(x, w, b, f43k=sl, **kw)
+    u = K.conv2d_nhwc(x, w, b, winograd="f43", out=out_b, out_coff=4, **kw)
     assert torch.equal(a2, a3) and torch.equal(a2, a[..., 4:4 + Cout])
     ref = F.conv2d(x.permute(0, 3, 1, 2).double().cpu(), w.raw.permute(0, 3, 1, 2).double().cpu(), b.double().cpu(), padding=1).permute(0, 2, 3, 1)
     if res:
