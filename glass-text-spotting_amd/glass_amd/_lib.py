@@ -32,6 +32,7 @@ EXPORTS = [
     "glass_bilstm_persistent_workspace_bytes", "glass_bilstm_recurrence_persistent", "glass_recurrence_status", "glass_recurrence_test_hook",
     "glass_decode_persistent_supported", "glass_decode_persistent_workspace_bytes", "glass_attention_decode_persistent",
     "glass_decode_workspace_bytes", "glass_attention_decode", "glass_decode_step_workspace_bytes", "glass_attention_decode_step",
+    "glass_lexicon_match_workspace_bytes", "glass_lexicon_match",
 ]
 
 
@@ -50,7 +51,8 @@ class GlassLibraryError(RuntimeError):
 DEVICE_FLAGS = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops", "-Xclang", "-target-feature", "-Xclang", "-fma-mix-insts"]
 
 
-ABI_VERSION = 8      # what csrc/common.hip glass_abi_version() returns: bumped whenever include/glass_hip.h gains or changes an entry
+ABI_VERSION = 8      # what csrc/common.hip glass_abi_version() returns: bumped only on an incompatible change of include/glass_hip.h
+                     # (an entry removed or its signature / meaning changed); added entries are found by symbol (lib() checks EXPORTS)
 
 
 def sources() -> List[str]:
@@ -128,6 +130,7 @@ def lib() -> ctypes.CDLL:
         L.glass_decode_step_workspace_bytes.restype = ctypes.c_int64
         L.glass_conv2d_splitk_workspace_bytes.restype = ctypes.c_int64
         L.glass_winograd43_splitk_workspace_bytes.restype = ctypes.c_int64
+        L.glass_lexicon_match_workspace_bytes.restype = ctypes.c_int64
         _LIB = L
     return _LIB
 

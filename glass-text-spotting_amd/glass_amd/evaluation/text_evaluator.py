@@ -1,6 +1,8 @@
 """Evaluation wire formats: what the reference's `TextEvaluator` writes, without its protocol.
 
-Host-side only (strings, JSON, zip): nothing here touches the GPU.  Mirrors, with the reference's names:
+Host-side (strings, JSON, zip), except for an optional `LexiconMatcher` (evaluation/lexicon.py) that a
+`TextResultWriter` may be given: lexicon replacement then runs as one batched GPU call instead of the host edit distance
+loop below.  Mirrors, with the reference's names:
   * `instances_to_coco_json`  - one record per recognised word: polys / boxes / rboxes / rec / score_text /
     character_probs / score_detection (glass/evaluation/text_evaluator.py:351-415),
   * `boxes_to_polygons`, `rotated_boxes_to_polygons` (:418-461),
@@ -231,16 +233,20 @@ def normalize_detection_line(line: str) -> Optional[str]:
 class TextResultWriter:
     """`TextEvaluator.process` / `to_eval_format` / `sort_detection` without files in the way: collect per-image
     records, then emit {file name -> lines} or a det.zip byte string.  `dataset` picks the reference's file naming
-    ('totaltext' / 'textocr': %07d.txt, 'icdar*': %d.txt) and image-id base (totaltext 0, others 1)."""
+    ('totaltext' / 'textocr': %07d.txt, 'icdar*': %d.txt) and image-id base (totaltext 0, others 1).
+    `matcher`: a LexiconMatcher built from the same `lexicon` / `pairs`; with it the lexicon replacement of
+    `to_eval_format` is one batched device call (same words, distances and rules); without it, `find_match_word` on the
+    host for every word."""
 
     def __init__(self, text_encoder, dataset: str = "icdar15", word_spotting: bool = False,
                  onlyRemoveFirstLastCharacter: bool = True, lexicon: Optional[Sequence[str]] = None,
                  pairs: Optional[Dict[str, str]] = None, lexicon_type: Optional[int] = None, edit_distance_thr: float = 1.5,
-                 masks_to_polygons: Optional[Callable] = None):
+                 masks_to_polygons: Optional[Callable] = None, matcher=None):
         self.text_encoder, self.dataset, self.word_spotting = text_encoder, dataset, word_spotting
         self.only_first_last = onlyRemoveFirstLastCharacter
         self.lexicon, self.pairs, self.lexicon_type, self.edit_distance_thr = lexicon, pairs, lexicon_type, edit_distance_thr
         self.masks_to_polygons = masks_to_polygons
+        self.matcher = matcher
         self._predictions: List[dict] = []
 
     def reset(self) -> None:
@@ -274,17 +280,24 @@ class TextResultWriter:
         score_text <= 0.001 are dropped, non-ASCII characters removed, optional lexicon replacement, transcript
         normalisation for lexicon / word-spotting runs, scores rounded to 3 digits BEFORE thresholding."""
         files: Dict[str, List[str]] = {}
-        for d in records:
-            if not d["score_text"] > 0.001:
-                continue
+        records = [d for d in records if d["score_text"] > 0.001]
+        per_image = self.lexicon_type == 3 and self.dataset.startswith("icdar")
+        matches = None
+        if self.lexicon and self.matcher is not None:          # every query of the call in one device launch
+            matches = self.matcher.match(["".join(c for c in d["rec"] if ord(c) < 128) for d in records],
+                                         [d["image_id"] if per_image else None for d in records])
+        for i, d in enumerate(records):
             cors = ",".join(f"{int(p[0])},{int(p[1])}" for p in d.get("polys", []))
             ass = "".join(c for c in d["rec"] if ord(c) < 128)
             if self.lexicon:
-                if self.lexicon_type == 3 and self.dataset.startswith("icdar"):
-                    lex, pairs = self.lexicon[d["image_id"]], self.pairs[d["image_id"]]
+                if matches is not None:
+                    word, dist = matches[i]
                 else:
-                    lex, pairs = self.lexicon, self.pairs
-                word, dist = find_match_word(ass, lex, pairs)
+                    if per_image:
+                        lex, pairs = self.lexicon[d["image_id"]], self.pairs[d["image_id"]]
+                    else:
+                        lex, pairs = self.lexicon, self.pairs
+                    word, dist = find_match_word(ass, lex, pairs)
                 if dist < self.edit_distance_thr or self.lexicon_type == 1:
                     ass = word
                 else:

@@ -13,6 +13,7 @@ import struct
 import threading
 from typing import List, NamedTuple, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .._lib import GlassLibraryError, check, lib
@@ -1350,3 +1351,53 @@ def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.T
         c_void_p(_dev(out["src"])), c_void_p(_dev(out["char"])), c_void_p(_dev(out["text_score"])),
         c_void_p(_dev(out["text_len"])), c_void_p(_dev(out["count"])), c_void_p(stream_handle())), "glass_postprocess_words")
     return out
+
+
+LEXICON_MAX_QUERY = 64        # symbols of one query: the bit-parallel pattern is one 64-bit word
+
+
+def lexicon_match(queries: Sequence[bytes], segments: Sequence[int], word_off: torch.Tensor, word_len: torch.Tensor,
+                  word_sym: torch.Tensor, word_index: torch.Tensor, seg_off: torch.Tensor, max_segment_words: int):
+    """Closest lexicon word of each query (glass_lexicon_match; reference lexicon_utils.py:4-28): queries are upper-cased
+    ASCII byte strings of <= 64 symbols, segments[q] the lexicon segment of query q; the lexicon is the device layout of
+    glass_amd.evaluation.lexicon.DeviceLexicon (int32 word_off / word_len / word_index / seg_off, uint8 word_sym).
+    -> (index, dist) int32 device tensors [Q]: the word_index of the best word and its distance, or -1 / 100."""
+    for name, t in (("word_off", word_off), ("word_len", word_len), ("word_index", word_index), ("seg_off", seg_off)):
+        _dev(t, name); _i32(t, name)
+    _dev(word_sym, "word_sym")
+    if word_sym.dtype != torch.uint8 or not word_sym.is_contiguous():
+        raise GlassLibraryError("word_sym must be contiguous uint8")
+    L, S = int(word_off.numel()), int(seg_off.numel()) - 1
+    if int(word_len.numel()) != L or int(word_index.numel()) != L or S < 0:
+        raise GlassLibraryError(f"lexicon layout: {L} offsets, {word_len.numel()} lengths, {word_index.numel()} indices, "
+                                f"{seg_off.numel()} segment bounds")
+    Q = len(queries)
+    if len(segments) != Q:
+        raise ValueError(f"{Q} queries but {len(segments)} segments")
+    lens = np.fromiter(map(len, queries), dtype=np.int32, count=Q)
+    if Q and int(lens.max()) > LEXICON_MAX_QUERY:
+        i = int(np.argmax(lens > LEXICON_MAX_QUERY))
+        raise ValueError(f"query {i} has {lens[i]} symbols (max {LEXICON_MAX_QUERY}): {bytes(queries[i])[:80]!r}")
+    flat = np.frombuffer(b"".join(bytes(b) for b in queries), dtype=np.uint8)
+    if flat.size and int(flat.max()) >= 128:
+        i = int(np.searchsorted(np.cumsum(lens), int(np.argmax(flat >= 128)), side="right"))
+        raise ValueError(f"query {i} is not ASCII: {bytes(queries[i])!r}")
+    q = np.zeros((Q, LEXICON_MAX_QUERY), dtype=np.uint8)
+    starts = np.cumsum(lens) - lens
+    q[np.repeat(np.arange(Q), lens), np.arange(flat.size) - np.repeat(starts, lens)] = flat
+    dev = word_off.device
+    index = torch.empty((Q,), dtype=torch.int32, device=dev)
+    dist = torch.empty((Q,), dtype=torch.int32, device=dev)
+    if Q == 0:
+        return index, dist
+    q_sym = upload(q, torch.uint8, dev)
+    q_len = upload(lens, torch.int32, dev)
+    q_seg = upload(np.asarray(segments, dtype=np.int32), torch.int32, dev)
+    L_ = lib()
+    ws_bytes = int(L_.glass_lexicon_match_workspace_bytes(Q))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+    check(L_.glass_lexicon_match(c_void_p(_dev(q_sym)), c_void_p(_dev(q_len)), c_void_p(_dev(q_seg)), Q, c_void_p(_dev(word_off)),
+                                 c_void_p(_dev(word_len)), c_void_p(_dev(word_sym)), c_void_p(_dev(word_index)), L,
+                                 c_void_p(_dev(seg_off)), S, int(max_segment_words), c_void_p(_dev(index)), c_void_p(_dev(dist)),
+                                 c_void_p(_dev(ws)), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_lexicon_match")
+    return index, dist

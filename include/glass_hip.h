@@ -505,6 +505,25 @@ int glass_attention_decode_step(const float* x, const float* xproj, const glass_
                                 const float* h_in, const int* y_prev, float* h_out, float* logits_out, float* probs_out,
                                 void* workspace, int64_t workspace_bytes, glass_stream_t stream);
 
+/* ------------------------------------------------------------------ lexicon matching (evaluation)
+ * find_match_word, un-weighted branch (glass/evaluation/lexicon_utils.py:4-28): for each query q, the word of lexicon segment
+ * q_segment[q] at the smallest unit-cost Levenshtein distance, first strict minimum in file order.  Symbols are bytes, both
+ * sides upper-cased by the caller; query bytes are < 128, and a lexicon code point >= 128 is stored as one sentinel byte >= 128
+ * (no query byte equals it, which gives exactly the distance over code points).
+ *   q_sym [Q][64] (4-byte aligned), q_len [Q] in 0..64, q_segment [Q] (a segment outside [0,S) is empty);
+ *   word i (segment order, may be sorted by length) = word_sym[word_off[i] .. word_off[i] + word_len[i]), every word_off[i] a
+ *   multiple of 16 and word_sym (16-byte aligned) readable in whole 16-byte pieces; word_index [L] >= 0 is word i's original
+ *   position, which breaks ties; segment s = words seg_off[s] .. seg_off[s+1]-1 (seg_off [S+1]).
+ *   max_segment_words (>= the largest segment's word count) sizes the grid.
+ * Result per query: out_index = word_index of the best word and out_dist its distance, or -1 / 100 when no word is closer
+ * than 100 (the reference's dist_min start value; an empty segment included).  `workspace` (8-byte aligned) >=
+ * glass_lexicon_match_workspace_bytes(Q).  Three launches; deterministic.                                                    */
+int64_t glass_lexicon_match_workspace_bytes(int Q);
+int glass_lexicon_match(const uint8_t* q_sym, const int* q_len, const int* q_segment, int Q, const int* word_off,
+                        const int* word_len, const uint8_t* word_sym, const int* word_index, int L, const int* seg_off, int S,
+                        int max_segment_words, int* out_index, int* out_dist, void* workspace, int64_t workspace_bytes,
+                        glass_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
