@@ -1,8 +1,11 @@
-"""Evaluation wire formats: what the reference's `TextEvaluator` writes, without its protocol.
+"""Evaluation wire formats: what the reference's `TextEvaluator` writes, and, through
+`TextResultWriter.evaluate`, what it returns.
 
 Host-side (strings, JSON, zip), except for an optional `LexiconMatcher` (evaluation/lexicon.py) that a
 `TextResultWriter` may be given: lexicon replacement then runs as one batched GPU call instead of the host edit distance
-loop below.  Mirrors, with the reference's names:
+loop below; and for the scoring, `TextResultWriter.evaluate(scorer)`, which hands the det.zip lines to an `RRCScorer`
+(evaluation/rrc_score.py: the official RRC protocol of `text_eval_script`, polygon geometry and matching on the GPU).
+Mirrors, with the reference's names:
   * `instances_to_coco_json`  - one record per recognised word: polys / boxes / rboxes / rec / score_text /
     character_probs / score_detection (glass/evaluation/text_evaluator.py:351-415),
   * `boxes_to_polygons`, `rotated_boxes_to_polygons` (:418-461),
@@ -12,8 +15,7 @@ loop below.  Mirrors, with the reference's names:
     per image, thresholded, clockwise, zipped as det.zip.
 `masks_to_polygons` (:464-492) is a pixel-edge ring tracer standing in for the rasterio + shapely polygoniser the
 reference uses (absent here); pass it (or your own) through `masks_to_polygons=`, otherwise the rotated box
-polygon is used.  The scoring itself (`text_eval_script`, the
-official RRC script) and dataset catalogues are out of scope.
+polygon is used.  Dataset catalogues and ground-truth download are out of scope.
 """
 from __future__ import annotations
 
@@ -22,6 +24,7 @@ import json
 import os
 import re
 import zipfile
+from collections import OrderedDict
 from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -325,6 +328,22 @@ class TextResultWriter:
                 lines = [normalize_detection_line(l) for l in files[name]]
                 z.writestr(name, "".join(l + "\n" for l in lines if l is not None))
         return buf.getvalue()
+
+    def evaluate(self, scorer, text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> "OrderedDict[str, Dict[str, float]]":
+        """`TextEvaluator.evaluate` (:245-295) without the files: coco_results -> to_eval_format -> per-line
+        normalisation (`sort_detection`) -> `scorer.score` (an `RRCScorer` holding the ground truth) ->
+        {'E2E_RESULTS': {'precision', 'recall', 'hmean'}, 'DETECTION_ONLY_RESULTS': {...}}; {} without predictions."""
+        from .rrc_score import parse_method_string
+        if len(self._predictions) == 0:
+            return OrderedDict()
+        files = self.to_eval_format(self.coco_results(), text_cf_th, detection_cf_th)
+        files = {name: [l for l in map(normalize_detection_line, lines) if l is not None] for name, lines in files.items()}
+        result = scorer.score(files, validate=False)       # the lines come straight from normalize_detection_line
+        out = OrderedDict()
+        for task in ("e2e_method", "det_only_method"):
+            name, values = parse_method_string(result[task])
+            out[name] = values
+        return out
 
     def write(self, output_dir: str, text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> Tuple[str, str]:
         os.makedirs(output_dir, exist_ok=True)

@@ -1401,3 +1401,82 @@ def lexicon_match(queries: Sequence[bytes], segments: Sequence[int], word_off: t
                                  c_void_p(_dev(seg_off)), S, int(max_segment_words), c_void_p(_dev(index)), c_void_p(_dev(dist)),
                                  c_void_p(_dev(ws)), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_lexicon_match")
     return index, dist
+
+
+def _typed(t: torch.Tensor, dtype: torch.dtype, name: str) -> torch.Tensor:
+    _dev(t, name)
+    if t.dtype != dtype or not t.is_contiguous():
+        raise GlassLibraryError(f"{name} must be contiguous {dtype} (got {t.dtype}, contiguous={t.is_contiguous()})")
+    return t
+
+
+def _rrc_layout(poly_off, gt_off, det_off, pair_off):
+    for name, t in (("poly_off", poly_off), ("gt_off", gt_off), ("det_off", det_off)):
+        _typed(t, torch.int32, name)
+    _typed(pair_off, torch.int64, "pair_off")
+    n_images = int(gt_off.numel()) - 1
+    if n_images < 0 or int(det_off.numel()) != n_images + 1 or int(pair_off.numel()) != n_images + 1 or poly_off.numel() < 1:
+        raise GlassLibraryError(f"rrc layout: {poly_off.numel()} polygon bounds, {gt_off.numel()} / {det_off.numel()} / "
+                                f"{pair_off.numel()} image bounds")
+    return int(poly_off.numel()) - 1, n_images
+
+
+def rrc_pair_areas(pts: torch.Tensor, poly_off: torch.Tensor, gt_off: torch.Tensor, det_off: torch.Tensor,
+                   pair_off: torch.Tensor, n_pairs: int):
+    """Polygon areas and the intersection area of every (GT, detection) pair of every image (glass_rrc_pair_areas; reference
+    text_eval_script.py:98-120): pts int32 [P, 2], poly_off int32 [n_poly + 1], gt_off / det_off int32 [I + 1] (polygon index
+    ranges of each image), pair_off int64 [I + 1] (running sum of G_i * D_i, n_pairs its last entry), all on the device.
+    -> (area [n_poly], inter [n_pairs]) float64 device tensors; inter of image i is row-major [G_i, D_i] at pair_off[i]."""
+    _typed(pts, torch.int32, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 2:
+        raise GlassLibraryError(f"pts must be [P, 2] (got {tuple(pts.shape)})")
+    n_poly, n_images = _rrc_layout(poly_off, gt_off, det_off, pair_off)
+    dev = poly_off.device
+    area = torch.empty((n_poly,), dtype=torch.float64, device=dev)
+    inter = torch.empty((int(n_pairs),), dtype=torch.float64, device=dev)
+    if n_poly == 0:
+        return area, inter
+    L_ = lib()
+    ws_bytes = int(L_.glass_rrc_pair_areas_workspace_bytes(n_poly))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+    check(L_.glass_rrc_pair_areas(c_void_p(pts.data_ptr()), ctypes.c_int64(int(pts.shape[0])), c_void_p(poly_off.data_ptr()), n_poly,
+                                  c_void_p(gt_off.data_ptr()), c_void_p(det_off.data_ptr()), c_void_p(pair_off.data_ptr()), n_images,
+                                  ctypes.c_int64(int(n_pairs)), c_void_p(area.data_ptr()), c_void_p(inter.data_ptr()),
+                                  c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_rrc_pair_areas")
+    return area, inter
+
+
+def rrc_match(area: torch.Tensor, inter: torch.Tensor, pair_off: torch.Tensor, gt_off: torch.Tensor, det_off: torch.Tensor,
+              gt_dontcare_e2e: torch.Tensor, gt_dontcare_det: torch.Tensor, n_det: int):
+    """The protocol's decisions on the pair areas (glass_rrc_match; reference text_eval_script.py:339-357, 374-409) for the
+    end-to-end and the detection-only care sets: gt_dontcare_* uint8 [n_gt], indexed by polygon index - gt_off[0];
+    n_det = det_off[-1] - det_off[0].  -> (det_dontcare_e2e, det_dontcare_det uint8 [n_det], match_e2e, match_det int32
+    [n_gt]): match[g] is the detection (counted within the image) GT g takes, or -1."""
+    _typed(area, torch.float64, "area"); _typed(inter, torch.float64, "inter")
+    _typed(gt_dontcare_e2e, torch.uint8, "gt_dontcare_e2e"); _typed(gt_dontcare_det, torch.uint8, "gt_dontcare_det")
+    for name, t in (("gt_off", gt_off), ("det_off", det_off)):
+        _typed(t, torch.int32, name)
+    _typed(pair_off, torch.int64, "pair_off")
+    n_images = int(gt_off.numel()) - 1
+    n_gt, n_det = int(gt_dontcare_e2e.numel()), int(n_det)
+    if n_images < 0 or int(det_off.numel()) != n_images + 1 or int(pair_off.numel()) != n_images + 1 or \
+            int(gt_dontcare_det.numel()) != n_gt:
+        raise GlassLibraryError(f"rrc layout: {gt_off.numel()} / {det_off.numel()} / {pair_off.numel()} image bounds, "
+                                f"{n_gt} / {gt_dontcare_det.numel()} GT flags")
+    dev = area.device
+    det_dc_e2e = torch.zeros((n_det,), dtype=torch.uint8, device=dev)
+    det_dc_det = torch.zeros((n_det,), dtype=torch.uint8, device=dev)
+    match_e2e = torch.full((n_gt,), -1, dtype=torch.int32, device=dev)
+    match_det = torch.full((n_gt,), -1, dtype=torch.int32, device=dev)
+    if n_images == 0 or (n_gt == 0 and n_det == 0):
+        return det_dc_e2e, det_dc_det, match_e2e, match_det
+    L_ = lib()
+    ws_bytes = int(L_.glass_rrc_match_workspace_bytes(n_det))
+    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
+    check(L_.glass_rrc_match(c_void_p(area.data_ptr()), int(area.numel()), c_void_p(inter.data_ptr()), ctypes.c_int64(int(inter.numel())),
+                             c_void_p(pair_off.data_ptr()), c_void_p(gt_off.data_ptr()), c_void_p(det_off.data_ptr()), n_images,
+                             c_void_p(gt_dontcare_e2e.data_ptr()), c_void_p(gt_dontcare_det.data_ptr()), n_gt, n_det,
+                             c_void_p(det_dc_e2e.data_ptr()), c_void_p(det_dc_det.data_ptr()), c_void_p(match_e2e.data_ptr()),
+                             c_void_p(match_det.data_ptr()), c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes),
+                             c_void_p(stream_handle())), "glass_rrc_match")
+    return det_dc_e2e, det_dc_det, match_e2e, match_det

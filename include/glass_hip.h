@@ -524,6 +524,36 @@ int glass_lexicon_match(const uint8_t* q_sym, const int* q_len, const int* q_seg
                         int max_segment_words, int* out_index, int* out_dist, void* workspace, int64_t workspace_bytes,
                         glass_stream_t stream);
 
+/* ------------------------------------------------------------------ RRC end-to-end scoring geometry (evaluation)
+ * The geometry and the decisions of text_eval_script.evaluate_method (glass/evaluation/text_eval_script.py): polygon
+ * area() and get_intersection (:98-120), the don't-care test of every detection (:339-357) and the greedy IoU matching
+ * (:374-409), for the end-to-end and the detection-only care sets.  Whether a matched pair is correct is a string question
+ * and stays with the caller.
+ *   polygons: integer rings in CSR form, pts [n_points][2] (x, y; 8-byte aligned), polygon k = points poly_off[k] ..
+ *   poly_off[k+1]-1 (poly_off [n_poly + 1]); simple rings of either orientation, convex or not, the first point may be
+ *   repeated at the end; |coordinate| <= 2^20.  Image i owns GT polygons gt_off[i] .. gt_off[i+1]-1 (G_i of them) and
+ *   detection polygons det_off[i] .. det_off[i+1]-1 (D_i); pair_off [n_images + 1] is the running sum of G_i * D_i and
+ *   n_pairs = pair_off[n_images].
+ * glass_rrc_pair_areas: area [n_poly] = |shoelace| / 2 (exact) and inter [n_pairs], row-major [G_i][D_i] per image at
+ *   pair_off[i]: the area of the intersection, fp64, exactly 0.0 when the bounding boxes do not overlap.  Bit-identical
+ *   from run to run (fixed-order sums, no atomics).  `workspace` (16-byte aligned) >=
+ *   glass_rrc_pair_areas_workspace_bytes(n_poly).  Two launches.
+ * glass_rrc_match: arrays over GT are indexed by (polygon index - gt_off[0]) and hold n_gt = gt_off[n_images] - gt_off[0]
+ *   entries, arrays over detections by (polygon index - det_off[0]), n_det entries.  gt_dontcare_* (in): the GT is outside
+ *   the care set.  det_dontcare_*[d] (out) = 1 iff a don't-care GT g of that set has inter(g,d) / area(d) > 0.5 (ratio 0 when
+ *   area(d) == 0).  match_*[g] (out) = the detection, counted within its image, that GT g takes, or -1: GT in order, each care
+ *   GT takes the lowest care, unmatched detection with inter / (area_g + area_d - inter) > 0.5 (0 when the union is 0).
+ *   `workspace` >= glass_rrc_match_workspace_bytes(n_det).  One launch, one workgroup per image.                        */
+int64_t glass_rrc_pair_areas_workspace_bytes(int n_poly);
+int glass_rrc_pair_areas(const int* pts, int64_t n_points, const int* poly_off, int n_poly, const int* gt_off, const int* det_off,
+                         const int64_t* pair_off, int n_images, int64_t n_pairs, double* area, double* inter, void* workspace,
+                         int64_t workspace_bytes, glass_stream_t stream);
+int64_t glass_rrc_match_workspace_bytes(int n_det);
+int glass_rrc_match(const double* area, int n_poly, const double* inter, int64_t n_pairs, const int64_t* pair_off, const int* gt_off,
+                    const int* det_off, int n_images, const uint8_t* gt_dontcare_e2e, const uint8_t* gt_dontcare_det, int n_gt,
+                    int n_det, uint8_t* det_dontcare_e2e, uint8_t* det_dontcare_det, int* match_e2e, int* match_det, void* workspace,
+                    int64_t workspace_bytes, glass_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
