@@ -15,7 +15,8 @@ Mirrors, with the reference's names:
     per image, thresholded, clockwise, zipped as det.zip.
 `masks_to_polygons` (:464-492) is a pixel-edge ring tracer standing in for the rasterio + shapely polygoniser the
 reference uses (absent here); pass it (or your own) through `masks_to_polygons=`, otherwise the rotated box
-polygon is used.  Dataset catalogues and ground-truth download are out of scope.
+polygon is used; `MaskPolygonizer` (evaluation/mask_rings.py) is the same tracer on the device, fed `pred_masks` without a
+host copy.  Dataset catalogues and ground-truth download are out of scope.
 """
 from __future__ import annotations
 
@@ -139,7 +140,9 @@ def instances_to_coco_json(instances, file_name, text_encoder, onlyRemoveFirstLa
     if len(instances) == 0:
         return []
     if instances.has("pred_masks") and masks_to_polygons is not None:
-        polygons = masks_to_polygons(instances.pred_masks.cpu().numpy())
+        masks = instances.pred_masks
+        # a callback that declares `takes_device_tensor` (MaskPolygonizer) gets the tensor where it lies
+        polygons = masks_to_polygons(masks if getattr(masks_to_polygons, "takes_device_tensor", False) else masks.cpu().numpy())
     else:
         b = instances.pred_boxes.tensor.cpu().numpy()
         polygons = (boxes_to_polygons(b) if b.shape[1] == 4 else rotated_boxes_to_polygons(b)).tolist()

@@ -1480,3 +1480,47 @@ def rrc_match(area: torch.Tensor, inter: torch.Tensor, pair_off: torch.Tensor, g
                              c_void_p(match_det.data_ptr()), c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes),
                              c_void_p(stream_handle())), "glass_rrc_match")
     return det_dc_e2e, det_dc_det, match_e2e, match_det
+
+
+MASK_RINGS_LDS_WORDS = 6144        # GLASS_MASK_RINGS_LDS_WORDS (include/glass_hip.h): a window of ceil(w / 64) * h 64-bit words at
+                                   # most is traced from a bitmap in LDS, a larger one from the labels in global memory
+
+
+def mask_rings(masks: torch.Tensor):
+    """Exterior ring of the largest 4-connected region of every mask, on the device (glass_mask_windows / glass_mask_rings_count
+    / glass_mask_rings_write, csrc/mask_rings.hip; reference text_evaluator.py:464-492, semantics of
+    glass_amd.evaluation.masks_to_polygons): masks contiguous bool / uint8 [R, H, W] on the device, non-zero = set.
+    -> (xy int32 [V, 2] (x, y on the pixel-corner lattice), ring_off int32 [R + 1]) device tensors; ring r is
+    xy[ring_off[r]:ring_off[r + 1]], closed, empty for an empty mask.
+    The host waits twice: for the windows (R x 4 integers, they size the workspace) and for the vertex total and the status
+    (they size xy); the masks themselves are never copied.  R == 0 launches nothing."""
+    _dev(masks, "masks")
+    if masks.dtype not in (torch.bool, torch.uint8) or not masks.is_contiguous() or masks.dim() != 3:
+        raise GlassLibraryError(f"masks must be contiguous bool / uint8 [R, H, W] (got {masks.dtype} {tuple(masks.shape)}, "
+                                f"contiguous={masks.is_contiguous()})")
+    R, H, W = (int(v) for v in masks.shape)
+    dev = masks.device
+    if R == 0:
+        return torch.empty((0, 2), dtype=torch.int32, device=dev), upload([0], torch.int32, dev)
+    if not (1 <= H <= 65535 and 1 <= W <= 65535 and H * W < 2 ** 31):
+        raise GlassLibraryError(f"masks of {H} x {W}: H, W must be in 1..65535 and H * W < 2^31")
+    L_ = lib()
+    st = c_void_p(stream_handle())
+    win = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    check(L_.glass_mask_windows(c_void_p(masks.data_ptr()), R, H, W, c_void_p(win.data_ptr()), st), "glass_mask_windows")
+    win_host = win.cpu()                                               # the host waits: the windows size the workspace
+    ws_bytes = int(L_.glass_mask_rings_workspace_bytes(c_void_p(win_host.data_ptr()), R, H, W))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+    meta = torch.empty((R + 2,), dtype=torch.int32, device=dev)        # ring_off [R + 1] | status
+    status = c_void_p(meta.data_ptr() + 4 * (R + 1))
+    check(L_.glass_mask_rings_count(c_void_p(masks.data_ptr()), R, H, W, c_void_p(win.data_ptr()), c_void_p(ws.data_ptr()),
+                                    ctypes.c_int64(ws_bytes), c_void_p(meta.data_ptr()), status, st), "glass_mask_rings_count")
+    total, code = (int(v) for v in meta[R:].cpu())                     # the host waits: the vertex total sizes xy
+    if code != 0:
+        raise GlassLibraryError(f"glass_mask_rings_count: status {code} (2 short workspace, 3 unclosed walk, 4 too many vertices)")
+    xy = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    if total:
+        check(L_.glass_mask_rings_write(R, H, W, c_void_p(win.data_ptr()), c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes),
+                                        c_void_p(meta.data_ptr()), c_void_p(xy.data_ptr()), ctypes.c_int64(total), status, st),
+              "glass_mask_rings_write")
+    return xy, meta[:R + 1]

@@ -554,6 +554,34 @@ int glass_rrc_match(const double* area, int n_poly, const double* inter, int64_t
                     int n_det, uint8_t* det_dontcare_e2e, uint8_t* det_dontcare_det, int* match_e2e, int* match_det, void* workspace,
                     int64_t workspace_bytes, glass_stream_t stream);
 
+/* ------------------------------------------------------------------ mask polygonisation (evaluation)
+ * masks_to_polygons (glass/evaluation/text_evaluator.py:464-492) without the masks leaving the device: for every mask of
+ * masks uint8 / bool [R][H][W] (non-zero = set; H, W in 1..65535, H * W < 2^31) the exterior ring of its largest 4-connected
+ * region on the pixel-corner lattice (x = column in [0, W], y = row in [0, H]).  The region with the most pixels wins, on a
+ * tie the one whose first pixel in raster order comes first; the ring starts at the top-left corner of that region's first
+ * raster pixel, heads east, keeps the region on its right-hand side (clockwise in image coordinates), has a vertex only
+ * where the boundary turns (a right turn where two pixels touch only diagonally, so that corner appears twice), ignores
+ * holes and repeats its first vertex at the end; an empty mask has no vertex.  Integer output, bit-identical from run to run.
+ * glass_mask_windows: windows int32 [R][4] (16-byte aligned) = x0, y0, x1, y1 (inclusive) of the set pixels of each mask,
+ *   x1 < x0 for an empty mask.  Two launches; the only stage that reads all of [R][H][W].
+ * glass_mask_rings_workspace_bytes: host function of a HOST copy of the windows: 8 bytes per window pixel and 20 per mask.
+ * glass_mask_rings_count: labels the windows (union-find; a region's root is its first raster pixel), picks the winners and
+ *   walks their rings once to count: ring_off int32 [R + 1] = running sum of the vertex counts.  *status (device) = 0, or
+ *   2 workspace smaller than the windows need, 3 a walk did not close within the window's edge count, 4 more than 2^31 - 1
+ *   vertices; ring_off is all zero then.  `workspace` (16-byte aligned) keeps the labels for glass_mask_rings_write.  Windows
+ *   of at most GLASS_MASK_RINGS_LDS_WORDS * 64 bits (rows padded to 64 columns) are traced from a bitmap in LDS, larger ones
+ *   from the labels in global memory.  Seven launches.
+ * glass_mask_rings_write: the same walk again, writing xy int32 [n_points][2] (x, y; 8-byte aligned), ring r at ring_off[r]
+ *   .. ring_off[r + 1] - 1, n_points >= ring_off[R]; same windows, workspace and ring_off as the count call.  *status = 3 if
+ *   a ring does not come out as long as counted (a workspace that is not the count call's).  One launch.                   */
+#define GLASS_MASK_RINGS_LDS_WORDS 6144
+int glass_mask_windows(const uint8_t* masks, int R, int H, int W, int* windows, glass_stream_t stream);
+int64_t glass_mask_rings_workspace_bytes(const int* windows_host, int R, int H, int W);
+int glass_mask_rings_count(const uint8_t* masks, int R, int H, int W, const int* windows, void* workspace, int64_t workspace_bytes,
+                           int* ring_off, int* status, glass_stream_t stream);
+int glass_mask_rings_write(int R, int H, int W, const int* windows, const void* workspace, int64_t workspace_bytes,
+                           const int* ring_off, int* xy, int64_t n_points, int* status, glass_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
