@@ -34,6 +34,7 @@ EXPORTS = [
     "glass_decode_workspace_bytes", "glass_attention_decode", "glass_decode_step_workspace_bytes", "glass_attention_decode_step",
     "glass_lexicon_match_workspace_bytes", "glass_lexicon_match",
     "glass_rrc_pair_areas_workspace_bytes", "glass_rrc_pair_areas", "glass_rrc_match_workspace_bytes", "glass_rrc_match",
+    "glass_rrc_sweep_workspace_bytes", "glass_rrc_sweep",
     "glass_mask_windows", "glass_mask_rings_workspace_bytes", "glass_mask_rings_count", "glass_mask_rings_write",
 ]
 
@@ -135,6 +136,7 @@ def lib() -> ctypes.CDLL:
         L.glass_lexicon_match_workspace_bytes.restype = ctypes.c_int64
         L.glass_rrc_pair_areas_workspace_bytes.restype = ctypes.c_int64
         L.glass_rrc_match_workspace_bytes.restype = ctypes.c_int64
+        L.glass_rrc_sweep_workspace_bytes.restype = ctypes.c_int64
         L.glass_mask_rings_workspace_bytes.restype = ctypes.c_int64
         _LIB = L
     return _LIB

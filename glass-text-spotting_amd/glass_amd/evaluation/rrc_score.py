@@ -226,6 +226,40 @@ def pair_correct(gt_transcription: str, det_transcription: str, word_spotting: b
     return g == d if word_spotting else transcription_match(g, d)
 
 
+MAX_SWEEP_COMBINATIONS = 1 << 20
+ACCEPT_WIDTH = 4                         # a ground truth accepts at most 4 strings: itself, without a first / a last / both special characters
+NO_WORD = -2                             # id of a detection string that no ground truth accepts (gt_accept pads with -1)
+
+
+def accepted_strings(gt_transcription: str, word_spotting: bool) -> List[str]:
+    """The detection strings (upper-cased) for which `pair_correct(gt_transcription, det, word_spotting)` holds."""
+    g = gt_transcription.upper().replace("####", "")
+    out = [g]
+    if not word_spotting and g != "":
+        first, last = g[0] in SPECIAL_CHARACTERS, g[-1] in SPECIAL_CHARACTERS
+        for ok, t in ((first, g[1:]), (last, g[:-1]), (first and last, g[1:-1])):
+            if ok and t not in out:
+                out.append(t)
+    return out
+
+
+def transcription_ids(samples: Sequence["GroundTruthSample"], det_transcriptions: Sequence[Sequence[str]],
+                      word_spotting: bool) -> Tuple[np.ndarray, np.ndarray]:
+    """Whether a matched pair is correct, as an integer question: (gt_accept int32 [n_gt, 4] padded with -1, det_word int32
+    [n_det]) over the ground truths of `samples` and the detections of `det_transcriptions` (one list per image), both
+    flattened in image order, with `det_word[d] in gt_accept[g]` <=> `pair_correct(gt g as compared, detection d,
+    word_spotting)` for EVERY pair.  A detection string no ground truth accepts gets NO_WORD.  Takes no tensors."""
+    ids: Dict[str, int] = {}
+    gts = [t for s in samples for t in s.transcriptions]
+    gt_accept = np.full((len(gts), ACCEPT_WIDTH), -1, dtype=np.int32)
+    for g, t in enumerate(gts):
+        for j, a in enumerate(accepted_strings(t, word_spotting)):
+            gt_accept[g, j] = ids.setdefault(a, len(ids))
+    det_word = np.fromiter((ids.get(t.upper(), NO_WORD) for image in det_transcriptions for t in image), dtype=np.int32,
+                           count=sum(len(image) for image in det_transcriptions))
+    return gt_accept, det_word
+
+
 # ------------------------------------------------------------------------------------------------------- tallies (host)
 
 class GroundTruthSample(NamedTuple):
@@ -470,6 +504,113 @@ class RRCScorer:
                 counts.append(c)
         e2e, det_only = method_strings(counts)
         return {"calculated": True, "Message": "", "e2e_method": e2e, "det_only_method": det_only, "per_sample": per_sample}
+
+
+    def sweep(self, scored_files, text_thresholds, detection_thresholds, validate: bool = True) -> "ThresholdSweep":
+        """`score()`'s two result lines for every pair (text_thresholds[i], detection_thresholds[j]) in one pass.
+        scored_files: {name: [(line, score_text, score_detection), ...]}, what `TextResultWriter.scored_lines` returns
+        after `normalize_detection_line`; in a combination a line is part of the submission iff
+        `not (score_text < text_th or score_detection < detection_th)` (fp64, a score equal to the threshold stays), as
+        `to_eval_format` decides.  The submission is encoded once and walked in the chunks of `score()`; per chunk the
+        pair areas, the don't-care marks and one `rrc_sweep` over all combinations; the counts are read back once.
+        `per_sample` is not built.  ValueError as `score()`, and for a bad grid (`threshold_grid`), before any launch."""
+        import torch
+        from ..ops import native as K
+        ts, ds = threshold_grid(text_thresholds, detection_thresholds)
+        files, scores = {}, {}
+        for name, entries in scored_files.items():
+            m = re.match(_DET_NAME, name)
+            if m is None:
+                raise ValueError("ZIP entry not valid: %s" % name)
+            lines = [str(e[0]) for e in entries]
+            if any(l.replace("\r", "").replace("\n", "") == "" for l in lines):
+                raise ValueError(f"empty line in {name}")
+            files[name], scores[m.group(1)] = lines, [(float(e[1]), float(e[2])) for e in entries]
+        enc = self.encode_submission(files, validate)
+        flat = np.array([p for key in self.keys for p in scores.get(key, [])], dtype=np.float64).reshape(-1, 2)
+        if not np.all(np.isfinite(flat)):
+            raise ValueError("scores must be finite")
+        G, D = self.n_gt_per_image, enc.n_det_per_image
+        assert flat.shape[0] == int(D.sum())
+        g_off, d_off = self._gt_off_host, np.concatenate([[0], np.cumsum(D)])
+        gt_accept, det_word = transcription_ids(self.samples, enc.det_transcriptions, self.word_spotting)
+        up = lambda a, t: (K.upload(np.ascontiguousarray(a), t, self.device) if a.size else
+                           torch.zeros(a.shape, dtype=t, device=self.device))
+        gt_accept, det_word = up(gt_accept, torch.int32).reshape(-1, ACCEPT_WIDTH), up(det_word, torch.int32)
+        score_text, score_det = up(flat[:, 0], torch.float64), up(flat[:, 1], torch.float64)
+        text_th, det_th = up(np.repeat(ts, ds.size), torch.float64), up(np.tile(ds, ts.size), torch.float64)   # k = i * D + j
+        counts = torch.zeros((ts.size * ds.size, 6), dtype=torch.int64, device=self.device)
+        for a, b in self.chunks(D):
+            pair_off = np.concatenate([[0], np.cumsum(G[a:b] * D[a:b])]).astype(np.int64)
+            n_pairs, n_det = int(pair_off[-1]), int(d_off[b] - d_off[a])
+            dev_pair_off = K.upload(pair_off, torch.int64, self.device)
+            gt_off, det_off = enc.gt_off[a:b + 1], enc.det_off[a:b + 1]
+            area, inter = K.rrc_pair_areas(enc.pts, enc.poly_off, gt_off, det_off, dev_pair_off, n_pairs)
+            g0, g1, d0, d1 = int(g_off[a]), int(g_off[b]), int(d_off[a]), int(d_off[b])
+            dc_e, dc_d, _, _ = K.rrc_match(area, inter, dev_pair_off, gt_off, det_off, self._gt_dc_e2e[g0:g1], self._gt_dc_det[g0:g1], n_det)
+            K.rrc_sweep(area, inter, dev_pair_off, gt_off, det_off, self._gt_dc_e2e[g0:g1], self._gt_dc_det[g0:g1], dc_e, dc_d,
+                        score_text[d0:d1], score_det[d0:d1], gt_accept[g0:g1], det_word[d0:d1], text_th, det_th, counts,
+                        max_dets=int(D[a:b].max()))
+        return ThresholdSweep(ts, ds, counts.cpu().numpy().reshape(ts.size, ds.size, 6))
+
+
+class ThresholdSweep:
+    """The protocol's result for every pair of a grid of confidence thresholds (`RRCScorer.sweep`).
+
+    text_thresholds [T], detection_thresholds [D]: the grid as given; counts int64 [T, D, 6]: the global sums in
+    `SampleCounts` order; e2e, det_only: {'precision', 'recall', 'hmean'} -> float64 [T, D], from `counts` with the
+    operations of `method_strings`, so a cell equals what `parse_method_string` reads from that combination's result line."""
+
+    TASKS = ("E2E_RESULTS", "DETECTION_ONLY_RESULTS")
+
+    def __init__(self, text_thresholds, detection_thresholds, counts: np.ndarray):
+        self.text_thresholds = np.asarray(text_thresholds, dtype=np.float64).reshape(-1)
+        self.detection_thresholds = np.asarray(detection_thresholds, dtype=np.float64).reshape(-1)
+        self.counts = np.asarray(counts, dtype=np.int64).reshape(len(self.text_thresholds), len(self.detection_thresholds), 6)
+        self.e2e = self._rates(self.counts[..., 0], self.counts[..., 1], self.counts[..., 2])
+        self.det_only = self._rates(self.counts[..., 3], self.counts[..., 4], self.counts[..., 5])
+
+    @classmethod
+    def empty(cls) -> "ThresholdSweep":
+        return cls(np.zeros(0), np.zeros(0), np.zeros((0, 0, 6), dtype=np.int64))
+
+    @staticmethod
+    def _rates(matched: np.ndarray, n_gt: np.ndarray, n_det: np.ndarray) -> Dict[str, np.ndarray]:
+        with np.errstate(divide="ignore", invalid="ignore"):
+            recall = np.where(n_gt == 0, 0.0, matched / n_gt)
+            precision = np.where(n_det == 0, 0.0, matched / n_det)
+            hmean = np.where(recall + precision == 0, 0.0, 2 * recall * precision / (recall + precision))
+        return {"precision": precision, "recall": recall, "hmean": hmean}
+
+    def results(self, i: int, j: int) -> "OrderedDict[str, Dict[str, float]]":
+        """What `TextResultWriter.evaluate(scorer, text_thresholds[i], detection_thresholds[j])` returns."""
+        return OrderedDict((task, {k: float(v[i, j]) for k, v in rates.items()})
+                           for task, rates in zip(self.TASKS, (self.e2e, self.det_only)))
+
+    def best(self, task: str = "E2E_RESULTS") -> Tuple[float, float, "OrderedDict[str, Dict[str, float]]"]:
+        """(text threshold, detection threshold, results) at the first maximum of `task`'s hmean in row-major order."""
+        if task not in self.TASKS:
+            raise ValueError(f"unknown task {task!r}")
+        hmean = (self.e2e if task == self.TASKS[0] else self.det_only)["hmean"]
+        if hmean.size == 0:
+            raise ValueError("the sweep is empty")
+        i, j = np.unravel_index(int(np.argmax(hmean)), hmean.shape)              # argmax: the first maximum
+        return float(self.text_thresholds[i]), float(self.detection_thresholds[j]), self.results(int(i), int(j))
+
+
+def threshold_grid(text_thresholds, detection_thresholds) -> Tuple[np.ndarray, np.ndarray]:
+    """The two lists as float64 vectors; ValueError for an empty list, a non-finite value or more than 2^20 combinations."""
+    out = []
+    for name, values in (("text", text_thresholds), ("detection", detection_thresholds)):
+        v = np.asarray(list(values), dtype=np.float64).reshape(-1)
+        if v.size == 0:
+            raise ValueError(f"no {name} threshold")
+        if not np.all(np.isfinite(v)):
+            raise ValueError(f"{name} thresholds must be finite: {v.tolist()}")
+        out.append(v)
+    if out[0].size * out[1].size > MAX_SWEEP_COMBINATIONS:
+        raise ValueError(f"{out[0].size} x {out[1].size} combinations, at most 2**20")
+    return out[0], out[1]
 
 
 def iou_matrix(inter: np.ndarray, area_gt: np.ndarray, area_det: np.ndarray) -> np.ndarray:

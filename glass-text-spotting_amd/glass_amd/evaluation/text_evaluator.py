@@ -281,11 +281,9 @@ class TextResultWriter:
                 out.append(x)
         return out
 
-    def to_eval_format(self, records: Sequence[dict], text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> Dict[str, List[str]]:
-        """records (coco_results) -> {"<id>.txt": ["x1,y1,...,####text", ...]} (:157-239): words with
-        score_text <= 0.001 are dropped, non-ASCII characters removed, optional lexicon replacement, transcript
-        normalisation for lexicon / word-spotting runs, scores rounded to 3 digits BEFORE thresholding."""
-        files: Dict[str, List[str]] = {}
+    def _eval_lines(self, records: Sequence[dict]):
+        """The lines of `to_eval_format` before any threshold, in its order: (file name, line, score_text, score_detection),
+        the two scores as it compares them (rounded to 3 digits, through their decimal string)."""
         records = [d for d in records if d["score_text"] > 0.001]
         per_image = self.lexicon_type == 3 and self.dataset.startswith("icdar")
         matches = None
@@ -317,10 +315,28 @@ class TextResultWriter:
                 name = "{}.txt".format(int(d["image_id"]))
             else:
                 raise ValueError(self.dataset)
+            yield name, cors + ",####" + ass, float(str(st)), float(str(sd))
+
+    def to_eval_format(self, records: Sequence[dict], text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> Dict[str, List[str]]:
+        """records (coco_results) -> {"<id>.txt": ["x1,y1,...,####text", ...]} (:157-239): words with
+        score_text <= 0.001 are dropped, non-ASCII characters removed, optional lexicon replacement, transcript
+        normalisation for lexicon / word-spotting runs, scores rounded to 3 digits BEFORE thresholding."""
+        files: Dict[str, List[str]] = {}
+        for name, line, st, sd in self._eval_lines(records):
             files.setdefault(name, [])
-            if float(str(st)) < text_cf_th or float(str(sd)) < detection_cf_th:
+            if st < text_cf_th or sd < detection_cf_th:
                 continue
-            files[name].append(cors + ",####" + ass)
+            files[name].append(line)
+        return files
+
+    def scored_lines(self, records: Sequence[dict]) -> Dict[str, List[Tuple[str, float, float]]]:
+        """What `to_eval_format` would emit if no threshold rejected anything, every line with the two numbers the
+        thresholds are compared with: {"<id>.txt": [(line, score_text, score_detection), ...]}, same files (those whose
+        lines would all be rejected included), same order.  `to_eval_format(records, t, d)` keeps exactly the lines with
+        `not (score_text < t or score_detection < d)`."""
+        files: Dict[str, List[Tuple[str, float, float]]] = {}
+        for name, line, st, sd in self._eval_lines(records):
+            files.setdefault(name, []).append((line, st, sd))
         return files
 
     def det_zip(self, files: Dict[str, List[str]]) -> bytes:
@@ -347,6 +363,21 @@ class TextResultWriter:
             name, values = parse_method_string(result[task])
             out[name] = values
         return out
+
+    def sweep(self, scorer, text_thresholds: Sequence[float], detection_thresholds: Sequence[float]):
+        """`evaluate` for every pair of a grid of thresholds in one pass (`RRCScorer.sweep`): the lines are formed and
+        normalised once (`scored_lines`, `normalize_detection_line`; a line it drops is dropped with its scores), the
+        geometry runs once, and the thresholds only select detections on the device.  -> `ThresholdSweep`; `results(i, j)`
+        is what `evaluate(scorer, text_thresholds[i], detection_thresholds[j])` returns.  Without predictions: the empty
+        sweep, as `evaluate` returns {}."""
+        from .rrc_score import ThresholdSweep
+        if len(self._predictions) == 0:
+            return ThresholdSweep.empty()
+        files = {}
+        for name, entries in self.scored_lines(self.coco_results()).items():
+            kept = [(normalize_detection_line(line), st, sd) for line, st, sd in entries]
+            files[name] = [e for e in kept if e[0] is not None]
+        return scorer.sweep(files, text_thresholds, detection_thresholds, validate=False)
 
     def write(self, output_dir: str, text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> Tuple[str, str]:
         os.makedirs(output_dir, exist_ok=True)

@@ -1482,7 +1482,58 @@ def rrc_match(area: torch.Tensor, inter: torch.Tensor, pair_off: torch.Tensor, g
     return det_dc_e2e, det_dc_det, match_e2e, match_det
 
 
-MASK_RINGS_LDS_WORDS = 6144        # GLASS_MASK_RINGS_LDS_WORDS (include/glass_hip.h): a window of ceil(w / 64) * h 64-bit words at
+RRC_SWEEP_LDS_WORDS = 4096         # GLASS_RRC_SWEEP_LDS_WORDS (include/glass_hip.h): an image's G x ceil(D / 64) row words are read
+                                   # from LDS up to this many, from the workspace above
+RRC_SWEEP_MAX_COMBINATIONS = 1 << 20
+
+
+def rrc_sweep(area: torch.Tensor, inter: torch.Tensor, pair_off: torch.Tensor, gt_off: torch.Tensor, det_off: torch.Tensor,
+              gt_dontcare_e2e: torch.Tensor, gt_dontcare_det: torch.Tensor, det_dontcare_e2e: torch.Tensor,
+              det_dontcare_det: torch.Tensor, det_score_text: torch.Tensor, det_score_det: torch.Tensor, gt_accept: torch.Tensor,
+              det_word: torch.Tensor, text_th: torch.Tensor, det_th: torch.Tensor, counts: torch.Tensor,
+              max_dets: Optional[int] = None) -> torch.Tensor:
+    """The protocol's tallies for K threshold combinations at once (glass_rrc_sweep, csrc/rrc_sweep.hip), ADDED into counts
+    int64 [K, 6] (SampleCounts order).  area .. gt_dontcare_* as for `rrc_match`; det_dontcare_* uint8 [n_det] as `rrc_match`
+    returned them for the same layout; det_score_* float64 [n_det]; gt_accept int32 [n_gt, 4] (padded with -1) and det_word
+    int32 [n_det]: a matched pair is correct iff det_word[d] >= 0 is one of gt_accept[g]; text_th / det_th float64 [K]:
+    detection d is present in combination k iff not (score_text[d] < text_th[k]) and not (score_det[d] < det_th[k]).
+    max_dets: the largest number of detections of one image (None: read back from det_off).  All on the device."""
+    _typed(area, torch.float64, "area"); _typed(inter, torch.float64, "inter")
+    for name, t in (("gt_dontcare_e2e", gt_dontcare_e2e), ("gt_dontcare_det", gt_dontcare_det), ("det_dontcare_e2e", det_dontcare_e2e),
+                    ("det_dontcare_det", det_dontcare_det)):
+        _typed(t, torch.uint8, name)
+    for name, t in (("gt_off", gt_off), ("det_off", det_off), ("gt_accept", gt_accept), ("det_word", det_word)):
+        _typed(t, torch.int32, name)
+    for name, t in (("det_score_text", det_score_text), ("det_score_det", det_score_det), ("text_th", text_th), ("det_th", det_th)):
+        _typed(t, torch.float64, name)
+    _typed(pair_off, torch.int64, "pair_off"); _typed(counts, torch.int64, "counts")
+    n_images, n_gt, n_det, n_comb = int(gt_off.numel()) - 1, int(gt_dontcare_e2e.numel()), int(det_dontcare_e2e.numel()), int(text_th.numel())
+    if n_images < 0 or int(det_off.numel()) != n_images + 1 or int(pair_off.numel()) != n_images + 1 or \
+            int(gt_dontcare_det.numel()) != n_gt or tuple(gt_accept.shape) != (n_gt, 4) or \
+            any(int(t.numel()) != n_det for t in (det_dontcare_det, det_score_text, det_score_det, det_word)):
+        raise GlassLibraryError(f"rrc layout: {gt_off.numel()} / {det_off.numel()} / {pair_off.numel()} image bounds, {n_gt} GT flags, "
+                                f"gt_accept {tuple(gt_accept.shape)}, {n_det} detection flags")
+    if not 1 <= n_comb <= RRC_SWEEP_MAX_COMBINATIONS or int(det_th.numel()) != n_comb or tuple(counts.shape) != (n_comb, 6):
+        raise GlassLibraryError(f"rrc_sweep: {n_comb} / {det_th.numel()} thresholds (1 .. 2^20), counts {tuple(counts.shape)}")
+    if n_images == 0 or (n_gt == 0 and n_det == 0):
+        return counts
+    if max_dets is None:
+        max_dets = int((det_off[1:] - det_off[:-1]).max())
+    L_ = lib()
+    ws_bytes = int(L_.glass_rrc_sweep_workspace_bytes(n_images, n_gt, n_det, ctypes.c_int64(int(inter.numel())), int(max_dets), n_comb))
+    ws = torch.empty((max(ws_bytes, 16) // 8,), dtype=torch.int64, device=area.device)
+    check(L_.glass_rrc_sweep(c_void_p(area.data_ptr()), int(area.numel()), c_void_p(inter.data_ptr()), ctypes.c_int64(int(inter.numel())),
+                             c_void_p(pair_off.data_ptr()), c_void_p(gt_off.data_ptr()), c_void_p(det_off.data_ptr()), n_images,
+                             c_void_p(gt_dontcare_e2e.data_ptr()), c_void_p(gt_dontcare_det.data_ptr()), n_gt,
+                             c_void_p(det_dontcare_e2e.data_ptr()), c_void_p(det_dontcare_det.data_ptr()),
+                             c_void_p(det_score_text.data_ptr()), c_void_p(det_score_det.data_ptr()), n_det, int(max_dets),
+                             c_void_p(gt_accept.data_ptr()), c_void_p(det_word.data_ptr()), c_void_p(text_th.data_ptr()),
+                             c_void_p(det_th.data_ptr()), n_comb, c_void_p(counts.data_ptr()), c_void_p(ws.data_ptr()),
+                             ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_rrc_sweep")
+    return counts
+
+
+MASK_RINGS_LDS_WORDS = 6144       # GLASS_MASK_RINGS_LDS_WORDS (include/glass_hip.h): a window of ceil(w / 64) * h 64-bit words at
                                    # most is traced from a bitmap in LDS, a larger one from the labels in global memory
 
 

@@ -554,6 +554,35 @@ int glass_rrc_match(const double* area, int n_poly, const double* inter, int64_t
                     int n_det, uint8_t* det_dontcare_e2e, uint8_t* det_dontcare_det, int* match_e2e, int* match_det, void* workspace,
                     int64_t workspace_bytes, glass_stream_t stream);
 
+/* ------------------------------------------------------------------ RRC threshold sweep (evaluation)
+ * The tallies of the decisions above for n_comb pairs of confidence thresholds at once, from one glass_rrc_pair_areas and
+ * one glass_rrc_match call: a threshold only removes detections, so the don't-care marks and the pair areas hold for every
+ * combination.  Same layout and indexing as glass_rrc_match (area, inter, pair_off, gt_off, det_off, gt_dontcare_*), plus
+ *   det_dontcare_* [n_det]: as glass_rrc_match wrote them for all detections of the same layout;
+ *   det_score_text, det_score_det fp64 [n_det]; max_dets >= every D_i (an image with more detections is skipped);
+ *   gt_accept int32 [n_gt][4] (16-byte aligned, padded with -1) and det_word int32 [n_det]: a matched pair (g, d) is correct
+ *   iff det_word[d] >= 0 and det_word[d] is one of gt_accept[g];
+ *   text_th, det_th fp64 [n_comb], 1 <= n_comb <= GLASS_RRC_SWEEP_MAX_COMBINATIONS, finite (the caller checks).
+ * In combination k detection d is present iff !(det_score_text[d] < text_th[k]) && !(det_score_det[d] < det_th[k]); the
+ * matching rule of glass_rrc_match runs on the present detections, separately for each care set.  counts int64 [n_comb][6]
+ * += over the images: end-to-end correct pairs, care GT, present care detections, then detection-only matched pairs, care
+ * GT, present care detections.  The kernel ADDS into counts (integer atomics: exact, identical from run to run), so the
+ * chunks of one sweep accumulate into one buffer that the caller zeroes first.
+ * `workspace` (16-byte aligned) >= glass_rrc_sweep_workspace_bytes(...): the G_i x D_i candidate matrices as 64-bit row
+ * words, the care words, and a mask slot per lane when max_dets > 512.  An image's rows are read from LDS when they fit
+ * GLASS_RRC_SWEEP_LDS_WORDS (32 KiB of the CU's 160 KiB: LDS does not limit the four workgroups per CU that the kernel's
+ * registers allow) and from the workspace otherwise.
+ * Two launches; no waiting between workgroups.                                                                             */
+#define GLASS_RRC_SWEEP_LDS_WORDS 4096
+#define GLASS_RRC_SWEEP_MAX_COMBINATIONS (1 << 20)
+int64_t glass_rrc_sweep_workspace_bytes(int n_images, int n_gt, int n_det, int64_t n_pairs, int max_dets, int n_comb);
+int glass_rrc_sweep(const double* area, int n_poly, const double* inter, int64_t n_pairs, const int64_t* pair_off, const int* gt_off,
+                    const int* det_off, int n_images, const uint8_t* gt_dontcare_e2e, const uint8_t* gt_dontcare_det, int n_gt,
+                    const uint8_t* det_dontcare_e2e, const uint8_t* det_dontcare_det, const double* det_score_text,
+                    const double* det_score_det, int n_det, int max_dets, const int* gt_accept, const int* det_word,
+                    const double* text_th, const double* det_th, int n_comb, int64_t* counts, void* workspace,
+                    int64_t workspace_bytes, glass_stream_t stream);
+
 /* ------------------------------------------------------------------ mask polygonisation (evaluation)
  * masks_to_polygons (glass/evaluation/text_evaluator.py:464-492) without the masks leaving the device: for every mask of
  * masks uint8 / bool [R][H][W] (non-zero = set; H, W in 1..65535, H * W < 2^31) the exterior ring of its largest 4-connected
