@@ -36,6 +36,7 @@ EXPORTS = [
     "glass_rrc_pair_areas_workspace_bytes", "glass_rrc_pair_areas", "glass_rrc_match_workspace_bytes", "glass_rrc_match",
     "glass_rrc_sweep_workspace_bytes", "glass_rrc_sweep",
     "glass_mask_windows", "glass_mask_rings_workspace_bytes", "glass_mask_rings_count", "glass_mask_rings_write",
+    "glass_ring_check_tasks", "glass_ring_check",
 ]
 
 
@@ -138,6 +139,7 @@ def lib() -> ctypes.CDLL:
         L.glass_rrc_match_workspace_bytes.restype = ctypes.c_int64
         L.glass_rrc_sweep_workspace_bytes.restype = ctypes.c_int64
         L.glass_mask_rings_workspace_bytes.restype = ctypes.c_int64
+        L.glass_ring_check_tasks.restype = ctypes.c_int64
         _LIB = L
     return _LIB
 

@@ -2,5 +2,6 @@ from .lexicon import DeviceLexicon, LexiconMatcher, encode_query, encode_word, l
 from .text_evaluator import (TextResultWriter, boxes_to_polygons, find_match_word, instances_to_coco_json,  # noqa: F401
                              levenshtein, masks_to_polygons, match_transcript, normalize_detection_line, rotated_boxes_to_polygons)
 from .mask_rings import MaskPolygonizer  # noqa: F401
+from .ring_check import RingChecker  # noqa: F401
 from .rrc_score import (RRCScorer, ThresholdSweep, include_in_dictionary, include_in_dictionary_transcription, load_gt_zip, method_strings,  # noqa: F401
                         parse_detection_line, parse_gt_line, tally_sample, transcription_match)

@@ -391,16 +391,19 @@ class RRCScorer:
 
     gt: what `load_gt_zip` returns, or a gt.zip path / bytes (then `line_format` as in `load_gt_zip`).
     chunk_images: at most this many images per device call (None: as many as fit `workspace_cap_bytes` of `inter`; one
-    image larger than the cap is a chunk of its own).  Chunking changes no result."""
+    image larger than the cap is a chunk of its own).  Chunking changes no result.
+    ring_checker: a RingChecker (evaluation/ring_check.py); with it the quadratic self-intersection test of `validate=True`
+    runs as one batched device check of all lines instead of once per line on the host (same errors for the same lines)."""
 
     def __init__(self, gt, word_spotting: bool, device, line_format: Optional[str] = None, chunk_images: Optional[int] = None,
-                 workspace_cap_bytes: int = WORKSPACE_CAP_BYTES):
+                 workspace_cap_bytes: int = WORKSPACE_CAP_BYTES, ring_checker=None):
         import torch
         from ..ops import native as K
         if not isinstance(gt, dict):
             gt = load_gt_zip(gt, line_format)
         self.word_spotting, self.device = bool(word_spotting), torch.device(device)
         self.chunk_images, self.workspace_cap_bytes = chunk_images, int(workspace_cap_bytes)
+        self.ring_checker = ring_checker
         if self.device.type != "cuda":
             raise K.GlassLibraryError(f"RRCScorer needs a HIP device (got {self.device}); the geometry has no CPU fallback")
         self.keys: List[str] = list(gt)
@@ -431,15 +434,32 @@ class RRCScorer:
                 raise ValueError("The sample %s not present in GT" % key)
         det_points: List[List[List[int]]] = [[] for _ in self.keys]
         det_trans: List[List[str]] = [[] for _ in self.keys]
+        batched = validate and self.ring_checker is not None
+        parsed: List[Tuple[str, str, List[int]]] = []      # (key, line, points) in the order the host path visits them
+
+        def first_crossing() -> None:
+            """the error of the first parsed line with crossing sides, as `parse_detection_line(line, True)` words it"""
+            verdicts = self.ring_checker.check_flat([p for _, _, p in parsed]) if parsed else []
+            for (key, line, _), v in zip(parsed, verdicts):
+                if v == 0:                                 # the linear checks passed, so 0 can only be a crossing
+                    e = ValueError(f"polygon has intersecting sides: {line!r}")
+                    raise ValueError(f"Line in sample not valid. Sample: {key} Line: {line} Error: {e}") from e
+
         for key, lines in subm.items():
             i = self._index[key]
             for line in lines:
                 try:
-                    p, t = parse_detection_line(line, validate)
+                    p, t = parse_detection_line(line, validate and not batched)
                 except ValueError as e:
+                    if batched:
+                        first_crossing()                   # a crossing in an earlier line is what the host path stops at
                     raise ValueError(f"Line in sample not valid. Sample: {key} Line: {line} Error: {e}") from e
+                if batched:
+                    parsed.append((key, line, p))
                 det_points[i].append(p)
                 det_trans[i].append(t)
+        if batched:
+            first_crossing()
         pts, poly_off = _flatten(det_points)
         n_det = np.array([len(p) for p in det_points], dtype=np.int64)
         det_off = self.n_gt + np.concatenate([[0], np.cumsum(n_det)])

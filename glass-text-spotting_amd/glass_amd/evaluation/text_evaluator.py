@@ -3,7 +3,9 @@
 
 Host-side (strings, JSON, zip), except for an optional `LexiconMatcher` (evaluation/lexicon.py) that a
 `TextResultWriter` may be given: lexicon replacement then runs as one batched GPU call instead of the host edit distance
-loop below; and for the scoring, `TextResultWriter.evaluate(scorer)`, which hands the det.zip lines to an `RRCScorer`
+loop below; for an optional `RingChecker` (evaluation/ring_check.py): the validity / winding test of `sort_detection` then
+runs as one batched GPU call for all lines instead of `normalize_detection_line` line by line; and for the scoring,
+`TextResultWriter.evaluate(scorer)`, which hands the det.zip lines to an `RRCScorer`
 (evaluation/rrc_score.py: the official RRC protocol of `text_eval_script`, polygon geometry and matching on the GPU).
 Mirrors, with the reference's names:
   * `instances_to_coco_json`  - one record per recognised word: polys / boxes / rboxes / rec / score_text /
@@ -242,17 +244,20 @@ class TextResultWriter:
     ('totaltext' / 'textocr': %07d.txt, 'icdar*': %d.txt) and image-id base (totaltext 0, others 1).
     `matcher`: a LexiconMatcher built from the same `lexicon` / `pairs`; with it the lexicon replacement of
     `to_eval_format` is one batched device call (same words, distances and rules); without it, `find_match_word` on the
-    host for every word."""
+    host for every word.
+    `ring_checker`: a RingChecker (evaluation/ring_check.py); with it `det_zip`, `evaluate` and `sweep` normalise all lines of
+    the call through one batched device check (same lines out); without it, `normalize_detection_line` line by line."""
 
     def __init__(self, text_encoder, dataset: str = "icdar15", word_spotting: bool = False,
                  onlyRemoveFirstLastCharacter: bool = True, lexicon: Optional[Sequence[str]] = None,
                  pairs: Optional[Dict[str, str]] = None, lexicon_type: Optional[int] = None, edit_distance_thr: float = 1.5,
-                 masks_to_polygons: Optional[Callable] = None, matcher=None):
+                 masks_to_polygons: Optional[Callable] = None, matcher=None, ring_checker=None):
         self.text_encoder, self.dataset, self.word_spotting = text_encoder, dataset, word_spotting
         self.only_first_last = onlyRemoveFirstLastCharacter
         self.lexicon, self.pairs, self.lexicon_type, self.edit_distance_thr = lexicon, pairs, lexicon_type, edit_distance_thr
         self.masks_to_polygons = masks_to_polygons
         self.matcher = matcher
+        self.ring_checker = ring_checker
         self._predictions: List[dict] = []
 
     def reset(self) -> None:
@@ -339,13 +344,22 @@ class TextResultWriter:
             files.setdefault(name, []).append((line, st, sd))
         return files
 
+    def _normalize_files(self, files: Dict[str, Sequence[str]], names: Sequence[str]) -> Dict[str, List[Optional[str]]]:
+        """{name: [normalize_detection_line(l) for l in files[name]]} for `names`, in their order; with a `ring_checker` all
+        lines of all files go through it in one call."""
+        if self.ring_checker is None:
+            return {name: [normalize_detection_line(l) for l in files[name]] for name in names}
+        done = iter(self.ring_checker.normalize_lines([l for name in names for l in files[name]]))
+        return {name: [next(done) for _ in files[name]] for name in names}
+
     def det_zip(self, files: Dict[str, List[str]]) -> bytes:
         """`sort_detection` (:96-155): per line validity / orientation normalisation, files zipped as det.zip."""
         buf = io.BytesIO()
+        names = sorted(files)
+        normalized = self._normalize_files(files, names)
         with zipfile.ZipFile(buf, "w", zipfile.ZIP_DEFLATED) as z:
-            for name in sorted(files):
-                lines = [normalize_detection_line(l) for l in files[name]]
-                z.writestr(name, "".join(l + "\n" for l in lines if l is not None))
+            for name in names:
+                z.writestr(name, "".join(l + "\n" for l in normalized[name] if l is not None))
         return buf.getvalue()
 
     def evaluate(self, scorer, text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> "OrderedDict[str, Dict[str, float]]":
@@ -356,7 +370,7 @@ class TextResultWriter:
         if len(self._predictions) == 0:
             return OrderedDict()
         files = self.to_eval_format(self.coco_results(), text_cf_th, detection_cf_th)
-        files = {name: [l for l in map(normalize_detection_line, lines) if l is not None] for name, lines in files.items()}
+        files = {name: [l for l in lines if l is not None] for name, lines in self._normalize_files(files, list(files)).items()}
         result = scorer.score(files, validate=False)       # the lines come straight from normalize_detection_line
         out = OrderedDict()
         for task in ("e2e_method", "det_only_method"):
@@ -373,10 +387,10 @@ class TextResultWriter:
         from .rrc_score import ThresholdSweep
         if len(self._predictions) == 0:
             return ThresholdSweep.empty()
-        files = {}
-        for name, entries in self.scored_lines(self.coco_results()).items():
-            kept = [(normalize_detection_line(line), st, sd) for line, st, sd in entries]
-            files[name] = [e for e in kept if e[0] is not None]
+        scored = self.scored_lines(self.coco_results())
+        normalized = self._normalize_files({name: [e[0] for e in entries] for name, entries in scored.items()}, list(scored))
+        files = {name: [(line, st, sd) for line, (_, st, sd) in zip(normalized[name], entries) if line is not None]
+                 for name, entries in scored.items()}
         return scorer.sweep(files, text_thresholds, detection_thresholds, validate=False)
 
     def write(self, output_dir: str, text_cf_th: float = 0.5, detection_cf_th: float = 0.0) -> Tuple[str, str]:

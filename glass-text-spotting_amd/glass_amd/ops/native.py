@@ -1575,3 +1575,50 @@ def mask_rings(masks: torch.Tensor):
                                         c_void_p(meta.data_ptr()), c_void_p(xy.data_ptr()), ctypes.c_int64(total), status, st),
               "glass_mask_rings_write")
     return xy, meta[:R + 1]
+
+
+RING_CHECK_MAX_COORD = 1 << 20    # glass_ring_check (include/glass_hip.h): |coordinate| and points per ring up to here keep
+RING_CHECK_MAX_POINTS = 1 << 20   # every determinant and shoelace sum exact in int64
+
+
+def ring_check_task_offsets(n_points_of_rings) -> np.ndarray:
+    """int64 [n_rings + 1]: running sum of glass_ring_check_tasks over the rings (the host helper is asked once per distinct
+    ring length, so Python and the kernel agree on the count without one foreign call per ring)."""
+    counts = np.asarray(n_points_of_rings, dtype=np.int64).reshape(-1)
+    L_ = lib()
+    lengths, inverse = np.unique(counts, return_inverse=True)
+    tasks = np.array([int(L_.glass_ring_check_tasks(int(n))) for n in lengths], dtype=np.int64)
+    off = np.zeros((counts.size + 1,), dtype=np.int64)
+    if counts.size:
+        np.cumsum(tasks[inverse], out=off[1:])
+    return off
+
+
+def ring_check(pts: torch.Tensor, ring_off_host):
+    """Validity and winding of integer rings (glass_ring_check, csrc/ring_check.hip; reference text_evaluator.py:112-137, the
+    rule of glass_amd.evaluation.normalize_detection_line): pts contiguous int32 [P, 2] on the device, ring_off_host [n_rings + 1]
+    host integers (non-decreasing, within 0..P), |coordinate| <= 2^20, at most 2^20 points per ring.
+    -> (verdict int32 [n_rings]: 0 drop / 1 keep / 2 keep reversed, area2 int64 [n_rings]: the shoelace sum) device tensors.
+    The offsets and the task table are uploaded stream-ordered; two launches on the current stream, none without rings."""
+    _typed(pts, torch.int32, "pts")
+    if pts.dim() != 2 or pts.shape[1] != 2:
+        raise GlassLibraryError(f"pts must be [P, 2] (got {tuple(pts.shape)})")
+    off = np.asarray(ring_off_host, dtype=np.int64).reshape(-1)
+    P, n_rings = int(pts.shape[0]), int(off.size) - 1
+    if n_rings < 0 or off[0] < 0 or off[-1] > P or np.any(np.diff(off) < 0):
+        raise GlassLibraryError(f"ring_off must hold n_rings + 1 non-decreasing offsets within 0..{P}")
+    if n_rings and int(np.diff(off).max()) > RING_CHECK_MAX_POINTS:
+        raise GlassLibraryError(f"a ring of {int(np.diff(off).max())} points, at most 2^20")
+    dev = pts.device
+    verdict = torch.empty((n_rings,), dtype=torch.int32, device=dev)
+    area2 = torch.empty((n_rings,), dtype=torch.int64, device=dev)
+    if n_rings == 0:
+        return verdict, area2
+    task_off = ring_check_task_offsets(np.diff(off))
+    n_tasks = int(task_off[-1])
+    dev_off = upload(off, torch.int32, dev)
+    dev_task = upload(task_off, torch.int64, dev)
+    check(lib().glass_ring_check(c_void_p(pts.data_ptr()), ctypes.c_int64(P), c_void_p(dev_off.data_ptr()), n_rings,
+                                 c_void_p(dev_task.data_ptr()), ctypes.c_int64(n_tasks), c_void_p(verdict.data_ptr()),
+                                 c_void_p(area2.data_ptr()), c_void_p(stream_handle())), "glass_ring_check")
+    return verdict, area2

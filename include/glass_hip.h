@@ -611,6 +611,29 @@ int glass_mask_rings_count(const uint8_t* masks, int R, int H, int W, const int*
 int glass_mask_rings_write(int R, int H, int W, const int* windows, const void* workspace, int64_t workspace_bytes,
                            const int* ring_off, int* xy, int64_t n_points, int* status, glass_stream_t stream);
 
+/* ------------------------------------------------------------------ detection ring validity and winding (evaluation)
+ * One line of sort_detection (glass/evaluation/text_evaluator.py:112-137) for all rings of a call: which rings are dropped
+ * and which are reversed.  Rings are integer rings in the CSR form of the scoring geometry above: pts [n_points][2] (x, y;
+ * 8-byte aligned), ring k = points ring_off[k] .. ring_off[k+1]-1 (ring_off [n_rings + 1], clamped to [0, n_points]);
+ * |coordinate| <= 2^20 and at most 2^20 points per ring, so that every determinant (< 2^43) and shoelace sum (< 2^62) is
+ * exact in int64.  No floating point.
+ * Per ring: area2 int64 = sum of x_i * y_{i+1} - x_{i+1} * y_i over the closed ring, and verdict int32 =
+ *   0 drop: fewer than 3 points, area2 == 0, or two sides properly cross;  1 keep as it stands: area2 < 0;
+ *   2 keep, reversed: area2 > 0.
+ * Side i is (p_i, p_{(i+1) mod n}); the pair (i, j) is tested for i + 2 <= j < n, except (0, n-1); sides (p,q), (r,s) properly
+ * cross iff orient(r,s,p), orient(r,s,q), orient(p,q,r), orient(p,q,s) are all non-zero, the first two differ in sign and the
+ * last two differ in sign.  Touching, collinear overlap, a repeated vertex and a zero-length side are no crossings.
+ * glass_ring_check_tasks (text_evaluator.py:112-137): host function, the number of pair-test tasks of a ring of n points:
+ *   B * (B + 1) / 2 with B = ceil(n / 64) for n >= 3, else 0.  task_off int64 [n_rings + 1] (device) is its running sum over
+ *   the rings and n_tasks = task_off[n_rings]; a task index that does not fit its ring is skipped.
+ * glass_ring_check (text_evaluator.py:112-137): two launches (areas and first verdicts, one wave per ring; pair tests, one
+ *   wave per task, so a long ring is spread over the grid); the second is omitted when n_tasks == 0.  A crossing clears the
+ *   verdict with an integer atomic: a ring's result depends neither on the other rings nor on the grid, and two runs are
+ *   bit-identical.  n_rings == 0 does nothing; n_points == 0 launches nothing and clears verdict and area2.              */
+int64_t glass_ring_check_tasks(int n_points_of_ring);
+int glass_ring_check(const int* pts, int64_t n_points, const int* ring_off, int n_rings, const int64_t* task_off, int64_t n_tasks,
+                     int* verdict, int64_t* area2, glass_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
