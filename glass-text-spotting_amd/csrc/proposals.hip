@@ -288,8 +288,9 @@ __global__ void box_decode_kernel(const float* cls, const float* deltas, const f
   const float dx = d[0] / wx, dy = d[1] / wy;
   float dw = d[2] / ww, dh = d[3] / wh;
   const float da = d[4] / wa;
-  dw = fminf(dw, SCALE_CLAMP);
-  dh = fminf(dh, SCALE_CLAMP);
+  // torch.clamp(max=): a NaN delta stays NaN (fminf would return SCALE_CLAMP, and the NMS filter could no longer drop the row)
+  dw = dw > SCALE_CLAMP ? SCALE_CLAMP : dw;
+  dh = dh > SCALE_CLAMP ? SCALE_CLAMP : dh;
   float* ob = out_boxes + 5 * r;
   ob[0] = dx * b[2] + b[0];
   ob[1] = dy * b[3] + b[1];

@@ -1273,7 +1273,9 @@ def attention_decode_step(x: torch.Tensor, xproj: torch.Tensor, weights: dict, h
 def detections_finalize(boxes: torch.Tensor, scores: torch.Tensor, orient: Optional[torch.Tensor],
                         text: Optional[torch.Tensor], counts: torch.Tensor, roi_start: Optional[torch.Tensor],
                         scale_xy: torch.Tensor, out_hw: torch.Tensor, min_box_dim: float, do_filter_small: bool):
-    """Batched meta-arch postprocess. boxes [N,K,5] ... -> (boxes, scores, orient|None, text|None, counts) padded."""
+    """Batched meta-arch postprocess. boxes [N,K,5] ... -> (boxes, scores, orient|None, text|None, counts) padded.
+    Image n uses its first min(counts[n], K) slots: a count above K is clamped to K.  The text row of slot j of image n is
+    text[roi_start[n] + j]; roi_start need not be contiguous (rows between two images are simply never read)."""
     N, K, _ = boxes.shape
     dev = boxes.device
     TC = int(text.shape[1] * text.shape[2]) if text is not None else 0
