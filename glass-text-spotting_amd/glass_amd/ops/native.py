@@ -1320,10 +1320,19 @@ def pack_word_records(words: dict, max_det: int, steps: int) -> torch.Tensor:
     return rec
 
 
+POSTPROCESS_LDS_MAX_K = 128      # csrc/postprocess.hip PP_KMAX: padded detections per image of the all-in-LDS kernel
+POSTPROCESS_MAX_K = 1024         # csrc/postprocess_dense.hip PD_KMAX (= NMS_KEEP_MAX and glass_detections_finalize's limit)
+
+
 def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.Tensor, text: Optional[torch.Tensor],
                       scale_xy: Optional[torch.Tensor], thresholds8: Sequence[float], stop_index: int) -> dict:
     """boxes [N,K,5], scores [N,K], counts int32 [N], text [N,K,T,C]|None -> dict of padded outputs (views of ONE zeroed
-    buffer: one fill launch instead of eight)."""
+    buffer: one fill launch instead of eight).  K <= POSTPROCESS_LDS_MAX_K runs the all-in-LDS kernel
+    (glass_postprocess_words), a wider K up to POSTPROCESS_MAX_K the dense one (glass_postprocess_words_dense) with its
+    pair-state workspace; same semantics, and the same bits where both apply."""
+    if boxes.dim() != 3 or int(boxes.shape[1]) > POSTPROCESS_MAX_K:
+        raise ValueError(f"postprocess_words: boxes {tuple(boxes.shape)}: needs [N, K, 5] with K <= {POSTPROCESS_MAX_K} "
+                         "detections per image")
     _f32c(boxes, "boxes"); _f32c(scores, "scores"); _i32(counts, "counts")
     N, K, _ = boxes.shape
     dev = boxes.device
@@ -1347,11 +1356,17 @@ def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.T
         arg, mx = text_argmax(text, counts)
     if scale_xy is not None:
         _f32c(scale_xy, "scale_xy")
-    check(lib().glass_postprocess_words(
-        c_void_p(_dev(boxes)), c_void_p(_dev(scores)), c_void_p(_dev(counts)), opt(arg), opt(mx), opt(scale_xy), N, K, T, thr,
-        int(stop_index), c_void_p(_dev(out["boxes"])), c_void_p(_dev(out["scores"])), c_void_p(_dev(out["polygons"])),
-        c_void_p(_dev(out["src"])), c_void_p(_dev(out["char"])), c_void_p(_dev(out["text_score"])),
-        c_void_p(_dev(out["text_len"])), c_void_p(_dev(out["count"])), c_void_p(stream_handle())), "glass_postprocess_words")
+    args = (c_void_p(_dev(boxes)), c_void_p(_dev(scores)), c_void_p(_dev(counts)), opt(arg), opt(mx), opt(scale_xy), N, K, T, thr,
+            int(stop_index), c_void_p(_dev(out["boxes"])), c_void_p(_dev(out["scores"])), c_void_p(_dev(out["polygons"])),
+            c_void_p(_dev(out["src"])), c_void_p(_dev(out["char"])), c_void_p(_dev(out["text_score"])),
+            c_void_p(_dev(out["text_len"])), c_void_p(_dev(out["count"])))
+    if K <= POSTPROCESS_LDS_MAX_K:
+        check(lib().glass_postprocess_words(*args, c_void_p(stream_handle())), "glass_postprocess_words")
+    else:
+        ws_bytes = int(lib().glass_postprocess_words_dense_workspace_bytes(N, K))
+        ws = torch.empty(((ws_bytes + 15) // 16 * 4,), dtype=torch.int32, device=dev)     # needs no initialisation
+        check(lib().glass_postprocess_words_dense(*args, c_void_p(_dev(ws)), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())),
+              "glass_postprocess_words_dense")
     return out
 
 

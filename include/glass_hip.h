@@ -359,6 +359,21 @@ int glass_postprocess_words(const float* boxes, const float* scores, const int* 
                             float* out_polygons, int* out_src, int* out_char, float* out_text_score, int* out_text_len,
                             int* out_count, glass_stream_t stream);
 
+/* The same post-processing (same reference call sites: post_processor_rotated_boxes.py:66-286, post_processor_academic.py:
+ * 26-35, text_evaluator.py:323-348) for up to 1024 padded detections per image, K <= 1024, T <= 64 - the width that
+ * glass_rotated_nms_select and glass_detections_finalize already deliver (TEST.DETECTIONS_PER_IMAGE of dense-text configs).
+ * Arguments and outputs as glass_postprocess_words; for inputs that fit both (K <= 128) the outputs are identical bit for
+ * bit.  One workgroup per image; the pair state (per box the last valid merge partners, and the pairs with IoU >= 0.99 of
+ * the NMS) lives in `workspace` (device memory, 16-byte aligned, >= glass_postprocess_words_dense_workspace_bytes(N, K) =
+ * N * 4 * (2 K + K (K - 1) / 2) bytes rounded up to 16 per image: 2.1 MB per image at K = 1024), which needs no
+ * initialisation and holds nothing afterwards.  Integer atomics only; results are identical from run to run.           */
+int64_t glass_postprocess_words_dense_workspace_bytes(int N, int K);
+int glass_postprocess_words_dense(const float* boxes, const float* scores, const int* counts, const int* text_arg,
+                                  const float* text_max, const float* scale_xy, int N, int K, int T,
+                                  const float* thresholds8_host, int stop_index, float* out_boxes, float* out_scores,
+                                  float* out_polygons, int* out_src, int* out_char, float* out_text_score, int* out_text_len,
+                                  int* out_count, void* workspace, int64_t workspace_bytes, glass_stream_t stream);
+
 /* The decode's argmax (reference glass/modeling/recognition/text_encoder.py:81-151 `preds_prob.max(dim=2)`, consumed by
  * text_evaluator.py:323-348): text [N,K,T,C] probability rows -> out_arg [N,K,T] first index of the row maximum,
  * out_max [N,K,T] the maximum; rows of boxes k >= counts[n] are skipped (outputs untouched).  One wavefront per row.  */
