@@ -33,6 +33,7 @@ EXPORTS = [
     "glass_decode_persistent_supported", "glass_decode_persistent_workspace_bytes", "glass_attention_decode_persistent",
     "glass_decode_workspace_bytes", "glass_attention_decode", "glass_decode_step_workspace_bytes", "glass_attention_decode_step",
     "glass_lexicon_match_workspace_bytes", "glass_lexicon_match",
+    "glass_lexicon_match_weighted_workspace_bytes", "glass_lexicon_match_weighted",
     "glass_rrc_pair_areas_workspace_bytes", "glass_rrc_pair_areas", "glass_rrc_match_workspace_bytes", "glass_rrc_match",
     "glass_rrc_sweep_workspace_bytes", "glass_rrc_sweep",
     "glass_mask_windows", "glass_mask_rings_workspace_bytes", "glass_mask_rings_count", "glass_mask_rings_write",
@@ -135,6 +136,12 @@ def lib() -> ctypes.CDLL:
         L.glass_conv2d_splitk_workspace_bytes.restype = ctypes.c_int64
         L.glass_winograd43_splitk_workspace_bytes.restype = ctypes.c_int64
         L.glass_lexicon_match_workspace_bytes.restype = ctypes.c_int64
+        L.glass_lexicon_match_weighted_workspace_bytes.restype = ctypes.c_int64
+        L.glass_lexicon_match_weighted_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
+        _p, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+        L.glass_lexicon_match_weighted.restype = ctypes.c_int
+        L.glass_lexicon_match_weighted.argtypes = [_p, _p, _p, _i, _p, _l, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i,
+                                                   _p, _p, _p, _p, _l, _p]
         L.glass_rrc_pair_areas_workspace_bytes.restype = ctypes.c_int64
         L.glass_rrc_match_workspace_bytes.restype = ctypes.c_int64
         L.glass_rrc_sweep_workspace_bytes.restype = ctypes.c_int64

@@ -1,6 +1,7 @@
-from .lexicon import DeviceLexicon, LexiconMatcher, encode_query, encode_word, lexicon_layout, load_lexicon  # noqa: F401
-from .text_evaluator import (TextResultWriter, boxes_to_polygons, find_match_word, instances_to_coco_json,  # noqa: F401
-                             levenshtein, masks_to_polygons, match_transcript, normalize_detection_line, rotated_boxes_to_polygons)
+from .lexicon import (DeviceLexicon, LexiconMatcher, WeightedLexiconMatcher, encode_query, encode_word, lexicon_layout,  # noqa: F401
+                      load_lexicon, symbol_classes, weighted_cost_tables)
+from .text_evaluator import (TextResultWriter, boxes_to_polygons, find_match_word, find_match_word_weighted,  # noqa: F401
+                             instances_to_coco_json, levenshtein, weighted_edit_distance, masks_to_polygons, match_transcript, normalize_detection_line, rotated_boxes_to_polygons)
 from .mask_rings import MaskPolygonizer  # noqa: F401
 from .ring_check import RingChecker  # noqa: F401
 from .rrc_score import (RRCScorer, ThresholdSweep, include_in_dictionary, include_in_dictionary_transcription, load_gt_zip, method_strings,  # noqa: F401

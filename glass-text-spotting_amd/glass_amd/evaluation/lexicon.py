@@ -6,6 +6,10 @@
     and kept on the device.
   * `LexiconMatcher` - `find_match_word` (:4-28, the un-weighted branch) for a whole batch of recognised words in one
     launch of glass_lexicon_match (csrc/lexicon.hip); `TextResultWriter(matcher=...)` uses it.
+  * `WeightedLexiconMatcher` - the weighted branch (:26-48 with `weighted_edit_distance`, :136-182; the evaluator's
+    TEST.LEXICON_WEIGHTED) through glass_lexicon_match_weighted (csrc/lexicon_weighted.hip): the host turns each record's
+    character probabilities into float64 cost tables (`weighted_cost_tables`), the device finds the candidates and runs
+    the DP; `TextResultWriter(matcher=..., weighted_ed=True)` uses it.
 
 Symbols: both sides are upper-cased with `str.upper()` as the reference does (once, at load, for the lexicon: it can
 change a word's length, e.g. 'ß' -> 'SS').  Queries are ASCII (the writer strips other characters first, `de_ascii`);
@@ -23,6 +27,8 @@ import torch
 SENTINEL = 0x80               # every non-ASCII lexicon code point
 MAX_QUERY = 64                # symbols of one query (one 64-bit pattern word on the device)
 NO_MATCH = ("", 100)          # find_match_word's answer when no word is closer than its dist_min start value
+NO_CLASS = 0xFF               # symbol -> class table entry of a symbol the text encoder has no class for
+WEIGHTED_TABLE_CAP_BYTES = 256 << 20      # most bytes of cost tables uploaded for one launch (RRCScorer's workspace cap)
 
 _LEXICON_DIR = os.path.join("evaluation", "lexicons")
 _FILES = {("totaltext", "weak"): ("totaltext/weak_voc_new.txt", "totaltext/weak_voc_pair_list.txt"),
@@ -154,8 +160,9 @@ class LexiconMatcher:
     def __init__(self, lexicon, pairs, device=None, weighted_ed: bool = False):
         if weighted_ed:
             raise NotImplementedError(
-                "weighted edit distance (LEXICON_WEIGHTED) is not built: upstream it cannot run - ed_replace_cost "
-                "(glass/evaluation/lexicon_utils.py:174-180) has no return, so any substitution adds None (TypeError)")
+                "LexiconMatcher is the unit-cost matcher; for the weighted edit distance (LEXICON_WEIGHTED, whose replace "
+                "cost is ed_replace_cost, glass/evaluation/lexicon_utils.py:174-180 and its return on :182) use "
+                "WeightedLexiconMatcher(lexicon, pairs, text_encoder)")
         self.lexicon = lexicon if isinstance(lexicon, DeviceLexicon) else DeviceLexicon(lexicon, device)
         self.pairs = pairs
 
@@ -176,4 +183,137 @@ class LexiconMatcher:
             else:
                 pairs = self.pairs if k is None else self.pairs[k]
                 out.append((pairs[self.lexicon.upper[i]], int(d)))
+        return out
+
+
+def symbol_classes(text_encoder) -> Tuple[np.ndarray, List[int]]:
+    """-> (sym_class uint8 [256], classes): sym_class[b] = position in `classes` of the class `char_encode` gives the
+    device symbol b (an ASCII character as is, SENTINEL for any non-ASCII character), NO_CLASS where it raises KeyError
+    (no '[UNK]'); `classes` = the distinct class ids met, ascending.  ValueError unless the character set is ASCII (a
+    non-ASCII character of the set would have to be told from the other non-ASCII characters, which share one symbol)."""
+    bad = [c for c in text_encoder.dict if len(c) == 1 and ord(c) >= 128]
+    if bad:
+        raise ValueError(f"the weighted matcher needs an ASCII character set; it holds {bad[:8]!r}")
+    ids = {}
+    for b in list(range(128)) + [SENTINEL]:
+        try:
+            ids[b] = int(text_encoder.char_encode(chr(b)))
+        except KeyError:
+            pass
+    classes = sorted(set(ids.values()))
+    if not classes or len(classes) >= NO_CLASS:
+        raise ValueError(f"{len(classes)} character classes (1..{NO_CLASS - 1})")
+    pos = {c: a for a, c in enumerate(classes)}
+    table = np.full(256, NO_CLASS, dtype=np.uint8)
+    for b, c in ids.items():
+        table[b] = pos[c]
+    return table, classes
+
+
+def weighted_cost_tables(rec: str, scores, text_encoder, classes: Sequence[int]):
+    """The costs `weighted_edit_distance(rec, word, scores, text_encoder)` adds, as float64 arrays, for m = len(rec):
+    del [m] (the query's own character's probability at each step), ins [m] (its mean with the next step's; the last
+    step: itself) and rep [m][len(classes)] = max(1 - scores[j][c] / del[j] * 5, 0) for c in `classes` (a pair of
+    characters equal up to case costs 0 instead; the caller tests that).  Same operations in the same order as the host
+    path, elementwise in float64, so the same bits.
+    Raises what the host path raises at its first substitution, before any of it runs: KeyError for a character of `rec`
+    without a class, IndexError for fewer score rows than characters, ZeroDivisionError for an own-character probability
+    of 0 - and ValueError for a negative or non-finite score (the device orders distances by their bit patterns)."""
+    m = len(rec)
+    A = len(classes)
+    if m == 0:
+        return np.zeros(0), np.zeros(0), np.zeros((0, A))
+    c1 = [text_encoder.char_encode(ch) for ch in rec]
+    S = np.asarray(scores, dtype=np.float64)
+    if S.ndim != 2:
+        raise ValueError(f"scores of shape {S.shape} ([steps][classes] expected)")
+    if m > S.shape[0]:
+        raise IndexError(f"{rec!r} has {m} characters but its scores have {S.shape[0]} rows")
+    S = S[:m]
+    if not (np.isfinite(S).all() and (S >= 0).all()):
+        raise ValueError(f"negative or non-finite character probability for {rec!r}")
+    own = S[np.arange(m), c1]                                # IndexError for a class beyond the row, as scores[j][c]
+    if (own == 0).any():
+        raise ZeroDivisionError(f"{rec!r}: probability 0 for its own character at step {int(np.argmax(own == 0))}")
+    ins = own.copy()
+    ins[:-1] = (own[:-1] + own[1:]) / 2
+    with np.errstate(over="ignore"):
+        rep = np.maximum(1 - S[:, list(classes)] / own[:, None] * 5, 0)
+    return own, ins, rep
+
+
+class WeightedLexiconMatcher:
+    """`find_match_word(rec, lexicon, pairs, scores, weighted_ed=True, text_encoder)` (lexicon_utils.py:26-48, :136-182)
+    for many words at once on the device: `match(strings, segments, scores)` -> [(pairs[word], weighted distance)],
+    ("", 100) when no candidate is closer than 100; `scores[i]` is record i's `character_probs` ([steps][classes], nested
+    lists or an array).  Lexicon, pairs and segments as for LexiconMatcher.  Distances are the host path's float64 values
+    bit for bit, and equal distances go to the first word in file order.
+
+    The one place it is stricter than the host path: the errors of `weighted_cost_tables` are raised for every non-empty
+    query before anything runs, where the host path meets them at the first substitution it computes (so not at all for a
+    query whose candidates are all empty words).  A candidate with a character the encoder has no class for (no '[UNK]')
+    raises KeyError after the launch, as `char_encode` does."""
+
+    weighted = True
+
+    def __init__(self, lexicon, pairs, text_encoder, device=None, table_cap_bytes: int = WEIGHTED_TABLE_CAP_BYTES):
+        self.lexicon = lexicon if isinstance(lexicon, DeviceLexicon) else DeviceLexicon(lexicon, device)
+        self.pairs = pairs
+        self.text_encoder = text_encoder
+        table, self.classes = symbol_classes(text_encoder)
+        self.sym_class = torch.from_numpy(table).to(self.lexicon.device)
+        self.table_cap_bytes = int(table_cap_bytes)
+
+    def _chunks(self, sizes: Sequence[int]) -> List[Tuple[int, int]]:
+        """[a, b) query ranges whose tables stay under table_cap_bytes (one query at least)"""
+        cap = max(self.table_cap_bytes // 8, 1)
+        out, a, total = [], 0, 0
+        for i, n in enumerate(sizes):
+            if i > a and total + n > cap:
+                out.append((a, i))
+                a, total = i, 0
+            total += n
+        if len(sizes) > a:
+            out.append((a, len(sizes)))
+        return out
+
+    def match(self, strings: Sequence[str], segments: Optional[Sequence[object]] = None, scores=None) -> List[Tuple[str, float]]:
+        from ..ops import native
+        if scores is None:
+            raise TypeError("match() needs scores=[character_probs of every string]")
+        keys = list(segments) if segments is not None else [None] * len(strings)
+        if len(keys) != len(strings):
+            raise ValueError(f"{len(strings)} strings but {len(keys)} segments")
+        if len(scores) != len(strings):
+            raise ValueError(f"{len(strings)} strings but {len(scores)} score tables")
+        queries = [encode_query(s) for s in strings]
+        seg = [self.lexicon.segment(k) for k in keys]
+        tables = []
+        for rec, sc in zip(strings, scores):                 # every error of the inputs is raised here, before any launch
+            d, i, r = weighted_cost_tables(rec, sc, self.text_encoder, self.classes)
+            tables.append(np.concatenate([d, i, r.reshape(-1)]))
+        t = self.lexicon.tensors
+        index, dist, status = [], [], []
+        for a, b in self._chunks([x.size for x in tables]):
+            sizes = np.fromiter((x.size for x in tables[a:b]), dtype=np.int64, count=b - a)
+            i, d, st = native.lexicon_match_weighted(queries[a:b], seg[a:b], np.concatenate(tables[a:b]), np.cumsum(sizes) - sizes,
+                                                     self.sym_class, len(self.classes), t["word_off"], t["word_len"], t["word_sym"],
+                                                     t["word_index"], t["seg_off"], self.lexicon.max_segment_words)
+            index += i.cpu().tolist()
+            dist += d.cpu().tolist()
+            status += st.cpu().tolist()
+        for q, st in enumerate(status):
+            if st & 2:
+                raise RuntimeError(f"glass_lexicon_match_weighted refused the tables of query {q} ({strings[q]!r})")
+            if st & 1:
+                raise KeyError(f"[UNK]: a candidate of {strings[q]!r} holds a character the text encoder has no class for")
+        out = []
+        for i, d, k, s in zip(index, dist, keys, strings):
+            if i < 0:
+                out.append(NO_MATCH)
+            else:
+                pairs = self.pairs if k is None else self.pairs[k]
+                word = self.lexicon.upper[i]
+                # the DP returns its integer border untouched when either word is empty, as the host path does
+                out.append((pairs[word], int(d) if (not s or not word) else d))
         return out

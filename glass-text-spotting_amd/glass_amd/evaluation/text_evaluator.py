@@ -11,8 +11,9 @@ Mirrors, with the reference's names:
   * `instances_to_coco_json`  - one record per recognised word: polys / boxes / rboxes / rec / score_text /
     character_probs / score_detection (glass/evaluation/text_evaluator.py:351-415),
   * `boxes_to_polygons`, `rotated_boxes_to_polygons` (:418-461),
-  * `match_transcript` (:299-321), `find_match_word` (lexicon_utils.py:4-49, plain edit distance; the python
-    `Levenshtein` package is replaced by `levenshtein` below),
+  * `match_transcript` (:299-321), `find_match_word` (lexicon_utils.py:4-25, plain edit distance; the python
+    `Levenshtein` package is replaced by `levenshtein` below), `find_match_word_weighted` / `weighted_edit_distance`
+    (lexicon_utils.py:26-48, :136-182: the LEXICON_WEIGHTED branch),
   * `TextResultWriter.to_eval_format` / `sort_detection` (:96-239): the RRC "x1,y1,...,xn,yn,####text" files, one
     per image, thresholded, clockwise, zipped as det.zip.
 `masks_to_polygons` (:464-492) is a pixel-edge ring tracer standing in for the rasterio + shapely polygoniser the
@@ -205,6 +206,53 @@ def find_match_word(rec_str: str, lexicon: Sequence[str], pairs: Dict[str, str])
     return match_word, match_dist
 
 
+def weighted_edit_distance(word1: str, word2: str, scores, text_encoder):
+    """MaskTextSpotterV3's weighted edit distance (lexicon_utils.py:136-182) between the recognised word `word1` and the
+    lexicon word `word2`, with `scores[j][c]` the recogniser's probability of class c at step j.  dp[0][j] = j,
+    dp[i][0] = i; consuming word2[i-1] without a query symbol costs ins[j-1], consuming word1[j-1] alone costs del[j-1],
+    pairing them costs 0 if they are equal up to case, else max(1 - p(word2[i-1]) / p(word1[j-1]) * 5, 0) at step j-1.
+    del[j] is the probability of the query's own character at j; ins[j] the mean of that and the next one (the last
+    step: itself).  Both depend on the query position only."""
+    m, n = len(word1), len(word2)
+    prev = list(range(m + 1))
+    for i in range(1, n + 1):
+        cur = [i]
+        ch2 = word2[i - 1]
+        for j in range(1, m + 1):
+            k = j - 1
+            own = scores[k][text_encoder.char_encode(word1[k])]
+            ins = (own + scores[k + 1][text_encoder.char_encode(word1[k + 1])]) / 2 if k < m - 1 else own
+            if word1[k].upper() != ch2.upper():
+                rep = max(1 - scores[k][text_encoder.char_encode(ch2)] / own * 5, 0)
+            else:
+                rep = 0
+            cur.append(min(prev[j] + ins, cur[j - 1] + own, prev[j - 1] + rep))
+        prev = cur
+    return prev[m]
+
+
+def find_match_word_weighted(rec_str: str, lexicon: Sequence[str], pairs: Dict[str, str], scores, text_encoder):
+    """`find_match_word(..., weighted_ed=True)` (lexicon_utils.py:26-48): the candidates are the distinct upper-cased
+    words within dist_min_pre + 2 unit edits of the upper-cased `rec_str`, dist_min_pre being the smallest unit distance
+    below 100 (100 if there is none, so words 100..102 away are candidates then); among them the first one, in file
+    order, with the strictly smallest `weighted_edit_distance(rec_str, word, ...)` below 100 wins.
+    -> (pairs[word], distance) or ("", 100)."""
+    rec = rec_str.upper()
+    unit = {}
+    for word in lexicon:
+        word = word.upper()
+        unit[word] = levenshtein(rec, word)                  # a repeated word keeps its first position
+    dist_min_pre = min([100] + list(unit.values()))
+    dist_min, match_word, match_dist = 100, "", 100
+    for word, ed in unit.items():
+        if ed > dist_min_pre + 2:
+            continue
+        d = weighted_edit_distance(rec_str, word, scores, text_encoder)
+        if d < dist_min:
+            dist_min, match_word, match_dist = d, pairs[word], d
+    return match_word, match_dist
+
+
 def _segments_cross(p, q, r, s) -> bool:
     def orient(a, b, c):
         return (b[0] - a[0]) * (c[1] - a[1]) - (b[1] - a[1]) * (c[0] - a[0])
@@ -245,14 +293,20 @@ class TextResultWriter:
     `matcher`: a LexiconMatcher built from the same `lexicon` / `pairs`; with it the lexicon replacement of
     `to_eval_format` is one batched device call (same words, distances and rules); without it, `find_match_word` on the
     host for every word.
+    `weighted_ed`: the reference's TEST.LEXICON_WEIGHTED: candidates are re-ranked with each record's `character_probs`
+    (`find_match_word_weighted`); the matcher, if given, must then be a WeightedLexiconMatcher.
     `ring_checker`: a RingChecker (evaluation/ring_check.py); with it `det_zip`, `evaluate` and `sweep` normalise all lines of
     the call through one batched device check (same lines out); without it, `normalize_detection_line` line by line."""
 
     def __init__(self, text_encoder, dataset: str = "icdar15", word_spotting: bool = False,
                  onlyRemoveFirstLastCharacter: bool = True, lexicon: Optional[Sequence[str]] = None,
                  pairs: Optional[Dict[str, str]] = None, lexicon_type: Optional[int] = None, edit_distance_thr: float = 1.5,
-                 masks_to_polygons: Optional[Callable] = None, matcher=None, ring_checker=None):
+                 masks_to_polygons: Optional[Callable] = None, matcher=None, ring_checker=None,
+                 weighted_ed: bool = False):
         self.text_encoder, self.dataset, self.word_spotting = text_encoder, dataset, word_spotting
+        self.weighted_ed = bool(weighted_ed)
+        if matcher is not None and bool(getattr(matcher, "weighted", False)) != self.weighted_ed:
+            raise ValueError("weighted_ed=True takes a WeightedLexiconMatcher, weighted_ed=False a LexiconMatcher")
         self.only_first_last = onlyRemoveFirstLastCharacter
         self.lexicon, self.pairs, self.lexicon_type, self.edit_distance_thr = lexicon, pairs, lexicon_type, edit_distance_thr
         self.masks_to_polygons = masks_to_polygons
@@ -293,8 +347,9 @@ class TextResultWriter:
         per_image = self.lexicon_type == 3 and self.dataset.startswith("icdar")
         matches = None
         if self.lexicon and self.matcher is not None:          # every query of the call in one device launch
+            extra = {"scores": [d["character_probs"] for d in records]} if self.weighted_ed else {}
             matches = self.matcher.match(["".join(c for c in d["rec"] if ord(c) < 128) for d in records],
-                                         [d["image_id"] if per_image else None for d in records])
+                                         [d["image_id"] if per_image else None for d in records], **extra)
         for i, d in enumerate(records):
             cors = ",".join(f"{int(p[0])},{int(p[1])}" for p in d.get("polys", []))
             ass = "".join(c for c in d["rec"] if ord(c) < 128)
@@ -306,7 +361,10 @@ class TextResultWriter:
                         lex, pairs = self.lexicon[d["image_id"]], self.pairs[d["image_id"]]
                     else:
                         lex, pairs = self.lexicon, self.pairs
-                    word, dist = find_match_word(ass, lex, pairs)
+                    if self.weighted_ed:
+                        word, dist = find_match_word_weighted(ass, lex, pairs, d["character_probs"], self.text_encoder)
+                    else:
+                        word, dist = find_match_word(ass, lex, pairs)
                 if dist < self.edit_distance_thr or self.lexicon_type == 1:
                     ass = word
                 else:

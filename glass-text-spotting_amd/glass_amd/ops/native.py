@@ -1373,6 +1373,23 @@ def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.T
 LEXICON_MAX_QUERY = 64        # symbols of one query: the bit-parallel pattern is one 64-bit word
 
 
+def _lexicon_queries(queries: Sequence[bytes]):
+    """byte strings -> ([Q][64] uint8 zero-padded, [Q] int32 lengths); ValueError for one over 64 symbols or not ASCII"""
+    Q = len(queries)
+    lens = np.fromiter(map(len, queries), dtype=np.int32, count=Q)
+    if Q and int(lens.max()) > LEXICON_MAX_QUERY:
+        i = int(np.argmax(lens > LEXICON_MAX_QUERY))
+        raise ValueError(f"query {i} has {lens[i]} symbols (max {LEXICON_MAX_QUERY}): {bytes(queries[i])[:80]!r}")
+    flat = np.frombuffer(b"".join(bytes(b) for b in queries), dtype=np.uint8)
+    if flat.size and int(flat.max()) >= 128:
+        i = int(np.searchsorted(np.cumsum(lens), int(np.argmax(flat >= 128)), side="right"))
+        raise ValueError(f"query {i} is not ASCII: {bytes(queries[i])!r}")
+    q = np.zeros((Q, LEXICON_MAX_QUERY), dtype=np.uint8)
+    starts = np.cumsum(lens) - lens
+    q[np.repeat(np.arange(Q), lens), np.arange(flat.size) - np.repeat(starts, lens)] = flat
+    return q, lens
+
+
 def lexicon_match(queries: Sequence[bytes], segments: Sequence[int], word_off: torch.Tensor, word_len: torch.Tensor,
                   word_sym: torch.Tensor, word_index: torch.Tensor, seg_off: torch.Tensor, max_segment_words: int):
     """Closest lexicon word of each query (glass_lexicon_match; reference lexicon_utils.py:4-28): queries are upper-cased
@@ -1391,17 +1408,7 @@ def lexicon_match(queries: Sequence[bytes], segments: Sequence[int], word_off: t
     Q = len(queries)
     if len(segments) != Q:
         raise ValueError(f"{Q} queries but {len(segments)} segments")
-    lens = np.fromiter(map(len, queries), dtype=np.int32, count=Q)
-    if Q and int(lens.max()) > LEXICON_MAX_QUERY:
-        i = int(np.argmax(lens > LEXICON_MAX_QUERY))
-        raise ValueError(f"query {i} has {lens[i]} symbols (max {LEXICON_MAX_QUERY}): {bytes(queries[i])[:80]!r}")
-    flat = np.frombuffer(b"".join(bytes(b) for b in queries), dtype=np.uint8)
-    if flat.size and int(flat.max()) >= 128:
-        i = int(np.searchsorted(np.cumsum(lens), int(np.argmax(flat >= 128)), side="right"))
-        raise ValueError(f"query {i} is not ASCII: {bytes(queries[i])!r}")
-    q = np.zeros((Q, LEXICON_MAX_QUERY), dtype=np.uint8)
-    starts = np.cumsum(lens) - lens
-    q[np.repeat(np.arange(Q), lens), np.arange(flat.size) - np.repeat(starts, lens)] = flat
+    q, lens = _lexicon_queries(queries)
     dev = word_off.device
     index = torch.empty((Q,), dtype=torch.int32, device=dev)
     dist = torch.empty((Q,), dtype=torch.int32, device=dev)
@@ -1418,6 +1425,70 @@ def lexicon_match(queries: Sequence[bytes], segments: Sequence[int], word_off: t
                                  c_void_p(_dev(seg_off)), S, int(max_segment_words), c_void_p(_dev(index)), c_void_p(_dev(dist)),
                                  c_void_p(_dev(ws)), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_lexicon_match")
     return index, dist
+
+
+def lexicon_match_weighted_launch(q_sym, q_len, q_seg, cost, cost_doubles, cost_off, sym_class, n_classes, max_query_len, word_off,
+                                  word_len, word_sym, word_index, seg_off, max_segment_words, index, dist, status) -> None:
+    """glass_lexicon_match_weighted on device tensors already laid out by `lexicon_match_weighted` (which checks them)"""
+    Q, L, S = int(q_len.numel()), int(word_off.numel()), int(seg_off.numel()) - 1
+    L_ = lib()
+    ws_bytes = int(L_.glass_lexicon_match_weighted_workspace_bytes(Q, int(max_segment_words)))
+    ws = torch.empty((max(ws_bytes // 8, 1),), dtype=torch.int64, device=word_off.device)
+    check(L_.glass_lexicon_match_weighted(
+        _dev(q_sym), _dev(q_len), _dev(q_seg), Q, _dev(cost), int(cost_doubles), _dev(cost_off), _dev(sym_class), int(n_classes),
+        int(max_query_len), _dev(word_off), _dev(word_len), _dev(word_sym), _dev(word_index), L, _dev(seg_off), S,
+        int(max_segment_words), _dev(index), _dev(dist), _dev(status), _dev(ws), ws_bytes, stream_handle()),
+        "glass_lexicon_match_weighted")
+
+
+def lexicon_match_weighted(queries: Sequence[bytes], segments: Sequence[int], cost: np.ndarray, cost_off: np.ndarray,
+                           sym_class: torch.Tensor, n_classes: int, word_off: torch.Tensor, word_len: torch.Tensor,
+                           word_sym: torch.Tensor, word_index: torch.Tensor, seg_off: torch.Tensor, max_segment_words: int):
+    """Weighted-edit-distance lexicon match (glass_lexicon_match_weighted; reference lexicon_utils.py:26-48, :136-182).
+    Queries, segments and the lexicon layout as for `lexicon_match`.  `cost` is one flat float64 host array with, for query
+    q of m symbols, del[m], ins[m] and rep[m][n_classes] from cost_off[q] on (int64 offsets in doubles); `sym_class` the
+    uint8 [256] device table word symbol -> class (>= n_classes: none).
+    -> (index int32, dist float64, status int32) device tensors [Q]: the word_index of the winner or -1, its weighted
+    distance or 100.0, and the status word (bit 0: a candidate has a symbol without a class; bit 1: bad table offset)."""
+    for name, t in (("word_off", word_off), ("word_len", word_len), ("word_index", word_index), ("seg_off", seg_off)):
+        _dev(t, name); _i32(t, name)
+    _dev(word_sym, "word_sym")
+    if word_sym.dtype != torch.uint8 or not word_sym.is_contiguous():
+        raise GlassLibraryError("word_sym must be contiguous uint8")
+    _dev(sym_class, "sym_class")
+    if sym_class.dtype != torch.uint8 or not sym_class.is_contiguous() or int(sym_class.numel()) != 256:
+        raise GlassLibraryError("sym_class must be 256 contiguous uint8")
+    L, S = int(word_off.numel()), int(seg_off.numel()) - 1
+    if int(word_len.numel()) != L or int(word_index.numel()) != L or S < 0:
+        raise GlassLibraryError(f"lexicon layout: {L} offsets, {word_len.numel()} lengths, {word_index.numel()} indices, "
+                                f"{seg_off.numel()} segment bounds")
+    Q = len(queries)
+    if len(segments) != Q:
+        raise ValueError(f"{Q} queries but {len(segments)} segments")
+    q, lens = _lexicon_queries(queries)
+    A = int(n_classes)
+    if not 1 <= A <= 255:
+        raise ValueError(f"{A} classes (1..255)")
+    cost = np.ascontiguousarray(cost, dtype=np.float64).reshape(-1)
+    cost_off = np.ascontiguousarray(cost_off, dtype=np.int64).reshape(-1)
+    if cost_off.size != Q:
+        raise ValueError(f"{Q} queries but {cost_off.size} table offsets")
+    if Q and (int(cost_off.min()) < 0 or int((cost_off + lens.astype(np.int64) * (A + 2)).max()) > cost.size):
+        raise ValueError(f"a query's cost tables lie outside the {cost.size} doubles given")
+    dev = word_off.device
+    index = torch.empty((Q,), dtype=torch.int32, device=dev)
+    dist = torch.empty((Q,), dtype=torch.float64, device=dev)
+    status = torch.empty((Q,), dtype=torch.int32, device=dev)
+    if Q == 0:
+        return index, dist, status
+    q_sym = upload(q, torch.uint8, dev)
+    q_len = upload(lens, torch.int32, dev)
+    q_seg = upload(np.asarray(segments, dtype=np.int32), torch.int32, dev)
+    d_cost = upload(cost if cost.size else np.zeros(1), torch.float64, dev)
+    d_off = upload(cost_off, torch.int64, dev)
+    lexicon_match_weighted_launch(q_sym, q_len, q_seg, d_cost, int(cost.size), d_off, sym_class, A, int(lens.max()), word_off,
+                                  word_len, word_sym, word_index, seg_off, int(max_segment_words), index, dist, status)
+    return index, dist, status
 
 
 def _typed(t: torch.Tensor, dtype: torch.dtype, name: str) -> torch.Tensor:

@@ -539,6 +539,30 @@ int glass_lexicon_match(const uint8_t* q_sym, const int* q_len, const int* q_seg
                         int max_segment_words, int* out_index, int* out_dist, void* workspace, int64_t workspace_bytes,
                         glass_stream_t stream);
 
+/* find_match_word, weighted branch (glass/evaluation/lexicon_utils.py:26-48, weighted_edit_distance :136-182; the evaluator's
+ * LEXICON_WEIGHTED).  Queries, lexicon layout and segments as for glass_lexicon_match.  Per query: dist_min_pre = the smallest
+ * unit distance (100 if none is smaller), candidates = the words at unit distance <= dist_min_pre + 2, result = the candidate
+ * with the smallest (weighted distance, word_index) among those below 100.  The weighted distance of query q (m symbols) and a
+ * word is the float64 DP dp[0][j] = j, dp[i][0] = i,
+ *   dp[i][j] = min(dp[i-1][j] + ins[j-1], dp[i][j-1] + del[j-1], dp[i-1][j-1] + (q_sym[j-1] == word[i-1] ? 0 : rep[j-1][a]))
+ * with a = sym_class[word[i-1]] and the query's tables at cost[q_cost_off[q] ..): del[m], ins[m], rep[m][A] (m * (A + 2)
+ * doubles; the whole block must lie inside cost[0 .. cost_doubles)).  sym_class [256]: class 0..A-1 of a word symbol, any
+ * value >= A for a symbol without one.  max_query_len >= every q_len (<= 64) sizes registers and LDS.  Only additions and
+ * minima run on the device, one cell at a time in the order written above, so the distance has the bits of the same DP in
+ * host float64.
+ * Result per query: out_index = word_index of the winner or -1, out_dist its distance or 100.0, out_status: bit 0 = a
+ * candidate of a non-empty query holds a symbol without a class (the reference's char_encode raises KeyError there), bit 1 =
+ * q_len or q_cost_off out of range (the query matches nothing).  `workspace` (8-byte aligned) >=
+ * glass_lexicon_match_weighted_workspace_bytes(Q, max_segment_words).  Four launches; deterministic, no floating-point
+ * atomics.                                                                                                                  */
+int64_t glass_lexicon_match_weighted_workspace_bytes(int Q, int max_segment_words);
+int glass_lexicon_match_weighted(const uint8_t* q_sym, const int* q_len, const int* q_segment, int Q, const double* cost,
+                                 int64_t cost_doubles, const int64_t* q_cost_off, const uint8_t* sym_class, int A,
+                                 int max_query_len, const int* word_off, const int* word_len, const uint8_t* word_sym,
+                                 const int* word_index, int L, const int* seg_off, int S, int max_segment_words, int* out_index,
+                                 double* out_dist, int* out_status, void* workspace, int64_t workspace_bytes,
+                                 glass_stream_t stream);
+
 /* ------------------------------------------------------------------ RRC end-to-end scoring geometry (evaluation)
  * The geometry and the decisions of text_eval_script.evaluate_method (glass/evaluation/text_eval_script.py): polygon
  * area() and get_intersection (:98-120), the don't-care test of every detection (:339-357) and the greedy IoU matching
