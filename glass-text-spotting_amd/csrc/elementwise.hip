@@ -45,7 +45,9 @@ __global__ __launch_bounds__(256) void maxpool_nhwc_kernel(const V4* __restrict_
         const int wi = w0 + kw;
         if ((unsigned)wi >= (unsigned)W) continue;
         const float4 v = mp_widen(xr[(long)wi * C4]);
-        m.x = fmaxf(m.x, v.x); m.y = fmaxf(m.y, v.y); m.z = fmaxf(m.z, v.z); m.w = fmaxf(m.w, v.w);
+        // IEEE-754-2019 maximum (v_maximum3_f32): a NaN tap gives NaN like F.max_pool2d - fmaxf would drop it
+        m.x = __builtin_elementwise_maximum(m.x, v.x); m.y = __builtin_elementwise_maximum(m.y, v.y);
+        m.z = __builtin_elementwise_maximum(m.z, v.z); m.w = __builtin_elementwise_maximum(m.w, v.w);
       }
     }
     mp_store(&y[(long)row * per_row + e], m);

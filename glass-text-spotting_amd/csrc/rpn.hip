@@ -215,8 +215,9 @@ __global__ __launch_bounds__(1024) void rpn_finalize_kernel(RpnBatch p) {
     const float dx = d[0] / p.wx, dy = d[1] / p.wy;
     float dw = d[2] / p.ww, dh = d[3] / p.wh;
     const float da = d[4] / p.wa;
-    dw = fminf(dw, SCALE_CLAMP);
-    dh = fminf(dh, SCALE_CLAMP);
+    // torch.clamp(max=): a NaN delta stays NaN (fminf would return SCALE_CLAMP, and the NMS filter could no longer drop the row)
+    dw = dw > SCALE_CLAMP ? SCALE_CLAMP : dw;
+    dh = dh > SCALE_CLAMP ? SCALE_CLAMP : dh;
     const long slot = (long)n * p.slots + lv.slot_off + j;
     float* ob = p.out_boxes + slot * 5;
     ob[0] = dx * aw + acx;

@@ -51,6 +51,84 @@ def ramp_roi_align_expected(box, out_hw, spatial_scale, ax, ay, c0):
     return out
 
 
+def roi_align_rotated_f64(feat, box, out_hw, spatial_scale, sampling_ratio):
+    """float64 RoIAlignRotated of one box on an arbitrary feature map feat [C, H, W] -> [C, PH, PW].
+
+    Written from the convention above plus detectron2's published sampling rule, not from an implementation:
+      * the box centre goes to index space as c * spatial_scale - 0.5, the box size as size * spatial_scale;
+      * each of the PH x PW bins holds g x g samples on a regular grid (bin offset (i + 0.5) / g), g = sampling_ratio, or
+        ceil(roi_h / PH) x ceil(roi_w / PW) samples when sampling_ratio is 0 (none at all for an empty box);
+      * a sample (offset rotated by `ccw_offset`) is SKIPPED when y < -1, y > H, x < -1 or x > W, otherwise it is clamped to
+        [0, H - 1] x [0, W - 1] and read bilinearly;
+      * the sum over the bin's samples is divided by max(sample count, 1) - skipped samples still count."""
+    feat = np.asarray(feat, dtype=np.float64)
+    C, H, W = feat.shape
+    cx, cy, w, h, a = [float(v) for v in box]
+    PH, PW = out_hw
+    cw, ch = cx * spatial_scale - 0.5, cy * spatial_scale - 0.5
+    rw, rh = w * spatial_scale, h * spatial_scale
+    gh = sampling_ratio if sampling_ratio > 0 else int(math.ceil(rh / PH))
+    gw = sampling_ratio if sampling_ratio > 0 else int(math.ceil(rw / PW))
+    count = max(gh * gw, 1)
+    out = np.zeros((C, PH, PW), dtype=np.float64)
+    for ph in range(PH):
+        for pw in range(PW):
+            acc = np.zeros((C,), dtype=np.float64)
+            for iy in range(gh):
+                dy = -rh / 2 + (ph + (iy + 0.5) / gh) * rh / PH
+                for ix in range(gw):
+                    dx = -rw / 2 + (pw + (ix + 0.5) / gw) * rw / PW
+                    ox, oy = ccw_offset(dx, dy, a)
+                    x, y = cw + ox, ch + oy
+                    if y < -1.0 or y > H or x < -1.0 or x > W:
+                        continue
+                    y, x = min(max(y, 0.0), H - 1.0), min(max(x, 0.0), W - 1.0)
+                    y0, x0 = int(math.floor(y)), int(math.floor(x))
+                    y1, x1 = min(y0 + 1, H - 1), min(x0 + 1, W - 1)
+                    ly, lx = y - y0, x - x0
+                    acc += ((1 - ly) * (1 - lx) * feat[:, y0, x0] + (1 - ly) * lx * feat[:, y0, x1] +
+                            ly * (1 - lx) * feat[:, y1, x0] + ly * lx * feat[:, y1, x1])
+            out[:, ph, pw] = acc / count
+    return out
+
+
+def roi_sample_points_f64(box, out_hw, spatial_scale, sampling_ratio):
+    """the (y, x) index-space sample points of `roi_align_rotated_f64`, [n, 2]"""
+    cx, cy, w, h, a = [float(v) for v in box]
+    PH, PW = out_hw
+    cw, ch = cx * spatial_scale - 0.5, cy * spatial_scale - 0.5
+    rw, rh = w * spatial_scale, h * spatial_scale
+    gh = sampling_ratio if sampling_ratio > 0 else int(math.ceil(rh / PH))
+    gw = sampling_ratio if sampling_ratio > 0 else int(math.ceil(rw / PW))
+    pts = []
+    for ph in range(PH):
+        for pw in range(PW):
+            for iy in range(gh):
+                for ix in range(gw):
+                    ox, oy = ccw_offset(-rw / 2 + (pw + (ix + 0.5) / gw) * rw / PW, -rh / 2 + (ph + (iy + 0.5) / gh) * rh / PH, a)
+                    pts.append((ch + oy, cw + ox))
+    return np.array(pts, dtype=np.float64).reshape(-1, 2)
+
+
+def bilinear_resize_f64(img, out_hw):
+    """float64 restatement of F.interpolate(mode='bilinear', align_corners=False) on img [C, H, W] -> [C, Ho, Wo]:
+    src = max(0, (dst + 0.5) * in / out - 0.5), i0 = floor(src), i1 = min(i0 + 1, in - 1), weight of i1 = src - i0."""
+    img = np.asarray(img, dtype=np.float64)
+    C, H, W = img.shape
+    Ho, Wo = out_hw
+
+    def axis(n_in, n_out):
+        src = np.maximum(0.0, (np.arange(n_out, dtype=np.float64) + 0.5) * (n_in / n_out) - 0.5)
+        i0 = np.minimum(np.floor(src).astype(np.int64), n_in - 1)
+        return i0, np.minimum(i0 + 1, n_in - 1), src - i0
+
+    y0, y1, ly = axis(H, Ho)
+    x0, x1, lx = axis(W, Wo)
+    top = img[:, y0][:, :, x0] * (1 - lx) + img[:, y0][:, :, x1] * lx
+    bot = img[:, y1][:, :, x0] * (1 - lx) + img[:, y1][:, :, x1] * lx
+    return top * (1 - ly)[None, :, None] + bot * ly[None, :, None]
+
+
 def _poly_area(p):
     x, y = p[:, 0], p[:, 1]
     return 0.5 * float(np.dot(x, np.roll(y, -1)) - np.dot(y, np.roll(x, -1)))

@@ -309,3 +309,71 @@ def test_reference_quadrant_logic_is_invariant_to_the_rect_form():
         boxes = [ref_box(c, (fw, fh), fa, o) for fw, fh, fa in forms]
         for b in boxes[1:]:
             np.testing.assert_allclose(b, boxes[0], atol=1e-9)
+
+
+# ------------------------------------------------------------------ float64 RoIAlign helper, on the GPU edge test's own inputs
+def test_roi_align_f64_helper_against_the_oracle_on_the_pool_edge_inputs():
+    """known_answers.roi_align_rotated_f64 (written from the documented convention and the published sampling rule) against
+    the oracle's fp32 C restatement on every box of tests/test_gpu_pool_edges.py's RoIAlign known-answer cases.  The GPU test
+    holds the kernel to 1e-4 of the helper; that is only meaningful while fp32 arithmetic itself stays well inside it, so
+    the oracle's distance is measured here and must stay below a quarter of it.  Measured: 3.3e-7 at most (the
+    adaptive-sampling boxes; 2.2e-7 for the rotated corner boxes, 1.5e-8 for the axis-aligned dyadic boundary cases)."""
+    import pool_edge_cases as P
+    from known_answers import roi_align_rotated_f64, roi_sample_points_f64
+    feat = P.roi_features()
+    f32 = torch.from_numpy(feat).float()[None]
+    assert torch.equal(f32.half().float(), f32), "the features must be fp16-representable"
+    worst = {}
+    for name, boxes, out_hw, sr in P.all_roi_cases():
+        rois = torch.cat([torch.zeros((len(boxes), 1)), torch.from_numpy(boxes).float()], dim=1)
+        assert np.array_equal(rois[:, 1:].double().numpy(), boxes), "box coordinates must be exact in fp32"
+        got = d2ops.roi_align_rotated(f32, rois, out_hw, 1.0, sr).double().numpy()
+        want = np.stack([roi_align_rotated_f64(feat, b, out_hw, 1.0, sr) for b in boxes])
+        assert np.isfinite(want).all() and np.isfinite(got).all()
+        worst[name] = float(np.abs(got - want).max())
+    print("oracle fp32 RoIAlign vs float64 helper, max |diff| per case:", worst)
+    assert max(worst.values()) < 0.25 * 1e-4, worst
+    # the cases are what they claim to be: a boundary box has a sample row / column exactly on its target, and the rule
+    # skips exactly the targets marked skipped (then the bins of that row / column lose those samples)
+    for sr, out_hw in P.BOUNDARY_CONFIGS:
+        for name, box, (ty, tx) in P.boundary_boxes(sr, out_hw):
+            pts = roi_sample_points_f64(box, out_hw, 1.0, sr)
+            assert ty is None or (pts[:, 0] == ty).any(), name
+            assert tx is None or (pts[:, 1] == tx).any(), name
+    for ts, n in ((P.boundary_targets(P.ROI_H), P.ROI_H), (P.boundary_targets(P.ROI_W), P.ROI_W)):
+        for t, skipped in ts[0] + ts[1]:
+            assert skipped == (t < -1.0 or t > n)
+    # degenerate boxes: nothing sampled -> exactly zero; the others are not all zero
+    for out_hw in P.DEGENERATE_OUT:
+        for box, empty in zip(P.DEGENERATE_BOXES, P.DEGENERATE_EMPTY):
+            v = roi_align_rotated_f64(feat, box, out_hw, 1.0, 0)
+            assert (np.abs(v).max() == 0.0) == empty, (box, out_hw)
+    # rotated corner boxes: no sample within 1e-3 of a skip limit (fp32 sin / cos move a sample by ~1e-5 at most), some
+    # samples skipped and some clamped in every box
+    for box in P.CORNER_BOXES:
+        pts = roi_sample_points_f64(box, P.CORNER_OUT, 1.0, P.CORNER_SR)
+        for col, n in ((0, P.ROI_H), (1, P.ROI_W)):
+            assert np.abs(pts[:, col] + 1.0).min() > 1e-3 and np.abs(pts[:, col] - n).min() > 1e-3, box
+        outside = (pts[:, 0] < -1) | (pts[:, 0] > P.ROI_H) | (pts[:, 1] < -1) | (pts[:, 1] > P.ROI_W)
+        assert outside.any() and not outside.all(), box
+
+
+def test_pool_edge_level_cases_are_robust_and_cover_every_boundary():
+    """the level-assignment list of tests/test_gpu_pool_edges.py: the expected level (numpy float32 evaluation of the
+    assign_boxes_to_levels formula) equals d2ops.assign_boxes_to_levels, survives a +-2 ulp error of log2 (so the GPU test
+    cannot hinge on the last bit of a device log2f), and the ulp and relative families have a case on each side of each
+    interior boundary, square and 4:1"""
+    import pool_edge_cases as P
+    cases = P.level_cases()
+    assert all(P.level_is_robust(w, h) for _, w, h, _ in cases)
+    boxes = torch.tensor([[0.0, 0.0, w, h, 0.0] for _, w, h, _ in cases])
+    got = d2ops.assign_boxes_to_levels(boxes, P.LEVEL_MIN, P.LEVEL_MIN + P.LEVEL_NUM - 1)
+    assert got.tolist() == [lv for *_, lv in cases]
+    for fam in ("ulp", "rel"):
+        for j, s in enumerate(P.LEVEL_BOUNDARIES):
+            for square in (True, False):
+                near = [(w, h, lv) for f, w, h, lv in cases if f == fam and (abs(w / h - 1.0) < 0.01) == square and
+                        abs(math.sqrt(w * h) / s - 1.0) < 5e-3]
+                assert {lv for *_, lv in near} == {j, j + 1}, (fam, s, square, near)
+    assert {lv for f, *_, lv in cases if f == "clamp"} == {0, P.LEVEL_NUM - 1}
+    assert sum(f == "exact" for f, *_ in cases) >= 4
