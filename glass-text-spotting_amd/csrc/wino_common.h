@@ -27,6 +27,8 @@ struct WinoParams {
   unsigned x_bytes, u_bytes, y_bytes, r_bytes;
   unsigned magic_tpi, magic_tw;    // floor(2^32 / d) for the two tile-index divisions (fast_div)
   unsigned long long* dbg;         // timing-instrumented builds only (GLASS_W43_ABL=4): per-workgroup cycle stamps
+  int nbody;                       // F(4x4) ragged mode (W = 4 k + 1): tiles [nbody, ntiles) are the paired last-column strip tiles; else = ntiles
+  unsigned magic_th;               // ... and floor(2^32 / TH) for their (image pair, tile row) division
 };
 
 __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(a.x + b.x, a.y + b.y, a.z + b.z, a.w + b.w); }

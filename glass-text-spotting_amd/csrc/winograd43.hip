@@ -151,11 +151,20 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino43_f32(WinoParams p) {
   {
     const int t = t0 + tl;
     const bool tv = t < p.ntiles;
-    const int n = fast_div(t, tpi, p.magic_tpi);
-    const int rem = t - n * tpi;
-    const int th = fast_div(rem, p.TW, p.magic_tw);
-    const int tw = rem - th * p.TW;
+    // ragged mode (W = 4 k + 1): tiles >= nbody are the paired strip tiles - tile row sth of images 2 sq (A) and 2 sq + 1 (B); the
+    // patch columns are (A col W-2, A col W-1, 0 | B col W-2, B col W-1, 0), so output column 0 is A's last pixel column and
+    // output column 3 is B's, through the same U and the same arithmetic as every other column.  B = A + one image: a column part.
+    const bool st = t >= p.nbody;
+    const int s = t - p.nbody;
+    const int sq = fast_div(s, p.TH, p.magic_th);
+    const int sth = s - sq * p.TH;
+    const int nb = fast_div(t, tpi, p.magic_tpi);
+    const int rem = t - nb * tpi;
+    const int thb = fast_div(rem, p.TW, p.magic_tw);
+    const int tw = rem - thb * p.TW;
+    const int n = st ? 2 * sq : nb, th = st ? sth : thb;
     const int h0 = 4 * th - 1, w0 = 4 * tw - 1;
+    const bool hasb = n + 1 < p.N;
 #pragma unroll
     for (int r = 0; r < 6; ++r) {
       const int hi = h0 + r;
@@ -163,8 +172,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino43_f32(WinoParams p) {
     }
 #pragma unroll
     for (int c = 0; c < 6; ++c) {
-      const int wi = w0 + c;
-      coloff[c] = ((unsigned)wi < (unsigned)p.W) ? (unsigned)((wi * p.ldx + 2 * c2) * 4) : INV;
+      const int wi = st ? (c % 3 == 2 || (c >= 3 && !hasb) ? -1 : (c >= 3 ? p.H * p.W : 0) + p.W - 2 + c % 3) : w0 + c;
+      coloff[c] = ((unsigned)wi < (unsigned)(st ? 2 * p.H * p.W : p.W)) ? (unsigned)((wi * p.ldx + 2 * c2) * 4) : INV;
     }
   }
   f32x2 dd[36];                               // the channel pair of the 6x6 patch, transformed in place
@@ -332,11 +341,19 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino43_f32(WinoParams p) {
   {
     const int t = t0 + vt;
     const bool tv = t < p.ntiles;
-    const int n = fast_div(t, tpi, p.magic_tpi);
-    const int rem = t - n * tpi;
-    const int th = fast_div(rem, p.TW, p.magic_tw);
-    const int tw = rem - th * p.TW;
-    const unsigned pix = (unsigned)((n * p.H + 4 * th) * p.W + 4 * tw);
+    // a paired strip tile (ragged mode, see the input role) keeps output column 0 -> column W-1 of image 2 sq and output
+    // column 3 -> the same pixel one image on (when that image exists); columns 1 and 2 mix the two images and are dropped
+    const bool st = t >= p.nbody;
+    const int s = t - p.nbody;
+    const int sq = fast_div(s, p.TH, p.magic_th);
+    const int sth = s - sq * p.TH;
+    const int nb = fast_div(t, tpi, p.magic_tpi);
+    const int rem = t - nb * tpi;
+    const int thb = fast_div(rem, p.TW, p.magic_tw);
+    const int tw = rem - thb * p.TW;
+    const int n = st ? 2 * sq : nb, th = st ? sth : thb;
+    const unsigned pix = (unsigned)((n * p.H + 4 * th) * p.W + (st ? p.W - 1 : 4 * tw));
+    const unsigned img = (unsigned)(p.H * p.W);
 #pragma unroll
     for (int a = 0; a < 4; ++a) {
       const bool ok = tv && 4 * th + a < p.H;
@@ -345,9 +362,10 @@ __global__ __launch_bounds__(256, 1) void conv3x3_wino43_f32(WinoParams p) {
     }
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
-      const bool ok = 4 * tw + b < p.W;
-      ycol[b] = ok ? (unsigned)b * ldy4 : INV;
-      rcol[b] = ok ? (unsigned)b * ldr4 : INV;
+      const bool ok = st ? (b == 0 || (b == 3 && n + 1 < p.N)) : 4 * tw + b < p.W;
+      const unsigned pb = st ? (b == 3 ? img : 0u) : (unsigned)b;
+      ycol[b] = ok ? pb * ldy4 : INV;
+      rcol[b] = ok ? pb * ldr4 : INV;
     }
   }
   // ReLU before (2) / after (1) the residual add as an unconditional max: max(x, qNaN) = x keeps "no ReLU" exact
@@ -528,12 +546,13 @@ extern "C" int glass_winograd43_pack_weights(const float* w, int Cout, int Cin, 
   return GLASS_OK;
 }
 
+enum { W43_FULL = 0, W43_BODY = 1, W43_RAGGED = 2 };   // every tile column | the full tile columns only | those + the paired last-column strip tiles
 static int wino43_launch(const glass_conv_desc* d, const float* x, const float* u_packed, const float* bias, const float* residual,
-                         float* y, glass_stream_t stream, bool body_only, int splits = 1, void* workspace = nullptr);
+                         float* y, glass_stream_t stream, int mode, int splits = 1, void* workspace = nullptr);
 
 extern "C" int glass_conv3x3_winograd43_nhwc(const glass_conv_desc* d, const float* x, const float* u_packed,
                                              const float* bias, const float* residual, float* y, glass_stream_t stream) {
-  return wino43_launch(d, x, u_packed, bias, residual, y, stream, false);
+  return wino43_launch(d, x, u_packed, bias, residual, y, stream, W43_FULL);
 }
 
 // Only the FULL 4-column tile columns: output columns [0, 4 * (W / 4)) of every row.  A map whose width is 4 k + 1 (the local
@@ -544,7 +563,28 @@ extern "C" int glass_conv3x3_winograd43_nhwc(const glass_conv_desc* d, const flo
 extern "C" int glass_conv3x3_winograd43_body_nhwc(const glass_conv_desc* d, const float* x, const float* u_packed,
                                                   const float* bias, const float* residual, float* y, glass_stream_t stream) {
   GLASS_CHECK_ARG(d && d->W >= 4, "glass_conv3x3_winograd43_body_nhwc: needs W >= 4");
-  return wino43_launch(d, x, u_packed, bias, residual, y, stream, true);
+  return wino43_launch(d, x, u_packed, bias, residual, y, stream, W43_BODY);
+}
+
+// Maps of width 4 k + 1 in ONE launch: the full tile columns as above, then ceil(N / 2) * TH paired strip tiles for the last pixel
+// column.  A strip tile's 6 patch columns are (A col W-2, A col W-1, 0, B col W-2, B col W-1, 0) for the images A = 2 q and
+// B = 2 q + 1 at the same tile row, so its output column 0 is A's column W-1 and its output column 3 is B's (columns 1 and 2 mix the
+// two images and are not stored): a 16 x 33 map pair costs 68 tiles instead of 64 + a strip launch, with the same packed U and
+// the same arithmetic for every column.  B is reached by adding one image stride to the column part of the split offsets, so the
+// spans must stay below 1 GiB with that stride added (glass_winograd43_ragged_supported).
+extern "C" int glass_winograd43_ragged_supported(const glass_conv_desc* d) {
+  if (!glass_winograd43_supported(d) || d->W % 4 != 1 || d->W < 5) return 0;
+  const long img = (long)d->H * d->W * 4, lim = 0x40000000L;
+  return ((long)d->N + 1) * img * d->ldx < lim && ((long)d->N + 1) * img * d->ldy < lim &&
+         (d->res_mode != 1 || ((long)d->N + 1) * img * d->ldr < lim);
+}
+
+extern "C" int glass_conv3x3_winograd43_ragged_nhwc(const glass_conv_desc* d, const float* x, const float* u_packed,
+                                                    const float* bias, const float* residual, float* y, glass_stream_t stream) {
+  GLASS_CHECK_ARG(d && glass_winograd43_ragged_supported(d),
+                  "glass_conv3x3_winograd43_ragged_nhwc: needs a layer glass_winograd43_supported() takes, W = 4 k + 1 >= 5 and operands "
+                  "+ one image < 1 GiB (got W=%d)", d ? d->W : 0);
+  return wino43_launch(d, x, u_packed, bias, residual, y, stream, W43_RAGGED);
 }
 
 // Split-K (round 6): the layers whose F(4x4) grid leaves most of the chip idle when ONE image is in flight (reference predictor:
@@ -574,11 +614,11 @@ extern "C" int glass_conv3x3_winograd43_splitk_nhwc(const glass_conv_desc* d, co
   GLASS_CHECK_ARG(workspace_bytes >= glass_winograd43_splitk_workspace_bytes(d, splits) && ((uintptr_t)workspace & 15) == 0,
                   "glass_conv3x3_winograd43_splitk_nhwc: workspace too small or not 16-byte aligned");
   GLASS_CHECK_ARG(!body_only || d->W >= 4, "glass_conv3x3_winograd43_splitk_nhwc: body_only needs W >= 4");
-  return wino43_launch(d, x, u_packed, bias, residual, y, stream, body_only != 0, splits, workspace);
+  return wino43_launch(d, x, u_packed, bias, residual, y, stream, body_only != 0 ? W43_BODY : W43_FULL, splits, workspace);
 }
 
 static int wino43_launch(const glass_conv_desc* d, const float* x, const float* u_packed, const float* bias, const float* residual,
-                         float* y, glass_stream_t stream, bool body_only, int splits, void* workspace) {
+                         float* y, glass_stream_t stream, int mode, int splits, void* workspace) {
   GLASS_CHECK_ARG(d && x && u_packed && y, "glass_conv3x3_winograd43_nhwc: null pointer");
   GLASS_CHECK_ARG(glass_winograd43_supported(d),
                   "glass_conv3x3_winograd43_nhwc: needs 3x3/stride 1/pad 1, Cin%%16==0, Cout%%64==0, unit channel stride, "
@@ -592,10 +632,13 @@ static int wino43_launch(const glass_conv_desc* d, const float* x, const float* 
   WinoParams p;
   p.x = x; p.u = u_packed; p.bias = bias; p.res = residual; p.y = y; p.dbg = nullptr;
   p.N = d->N; p.H = d->H; p.W = d->W; p.Cin = d->Cin; p.Cout = d->Cout;
-  p.TH = (d->H + 3) / 4; p.TW = body_only ? d->W / 4 : (d->W + 3) / 4;      // (input / output bounds still use the true W)
-  const long nt = (long)d->N * p.TH * p.TW;
+  p.TH = (d->H + 3) / 4; p.TW = mode != W43_FULL ? d->W / 4 : (d->W + 3) / 4;      // (input / output bounds still use the true W)
+  const long nbody = (long)d->N * p.TH * p.TW;
+  const long nt = nbody + (mode == W43_RAGGED ? ((long)d->N + 1) / 2 * p.TH : 0);       // + the paired last-column strip tiles
   GLASS_CHECK_ARG(nt < 0x7fffffffL, "glass_conv3x3_winograd43_nhwc: too many tiles");
   p.ntiles = (int)nt;
+  p.nbody = mode == W43_RAGGED ? (int)nbody : p.ntiles;
+  p.magic_th = (unsigned)(0x100000000ULL / (unsigned long long)p.TH);
   const bool wide = wino43_wide(d->Cout, d->Cin);
   const int T4 = wide ? 16 : 32, N4 = wide ? 128 : 64, K4 = wide ? 32 : 16;
   p.nkt = d->Cin / K4;

@@ -25,6 +25,7 @@ EXPORTS = [
     "glass_conv_h16_supported", "glass_conv_h16_weight_halves", "glass_conv_h16_pack_weights", "glass_conv2d_nhwc_h16_packed",
     "glass_winograd_supported", "glass_winograd_block_channels", "glass_winograd_weight_floats", "glass_winograd_pack_weights", "glass_conv3x3_winograd_nhwc",
     "glass_winograd43_supported", "glass_winograd43_weight_floats", "glass_winograd43_pack_weights", "glass_conv3x3_winograd43_nhwc",
+    "glass_winograd43_ragged_supported", "glass_conv3x3_winograd43_ragged_nhwc",
     "glass_maxpool2d_nhwc", "glass_maxpool2d_nhwc_h16", "glass_roi_align_rotated_h16", "glass_pixel_shuffle2x_nhwc", "glass_sigmoid_inplace", "glass_paste_rotated_masks", "glass_mul_inplace", "glass_cast_f32_to_f16",
     "glass_preprocess_image", "glass_image_u8hwc_to_chw_resized", "glass_roi_align_rotated",
     "glass_rpn_workspace_bytes", "glass_rpn_topk_decode", "glass_rotated_nms_select", "glass_pairwise_iou_rotated", "glass_detections_finalize", "glass_postprocess_words", "glass_postprocess_words_dense_workspace_bytes", "glass_postprocess_words_dense", "glass_text_argmax", "glass_pack_word_records",

@@ -114,6 +114,13 @@ def _parse_split(v) -> int:
     return n
 
 
+def _parse_ragged(v):
+    """False | True (= "strip") | "tiles" - see Routing.ragged; the environment's "0" / "strip" / anything else map to the three"""
+    if isinstance(v, str):
+        return {"0": False, "strip": True}.get(v, "tiles")
+    return bool(v)
+
+
 class Routing:
     """Which kernel a conv / linear launch takes, as VALUES that travel with the layer (no global state, re-entrant
     per model): a model builds one `Routing` at construction (environment variables GLASS_* give the defaults, `MODEL.
@@ -128,8 +135,11 @@ class Routing:
       h16         fp16 modes: the packed-weight fp16-MFMA kernel (GLASS_CONV_H16=0: fp32 template with fp16 operands)
       local_stem  the fused conv0_1 + conv0_2 + maxpool kernel of the local extractor (GLASS_LOCAL_STEM=0: three launches)
       stem        the fused 7x7 conv + ReLU + max-pool kernel of the ResNet stem (GLASS_BACKBONE_STEM=0: two launches)
-      ragged      maps of width 4 k + 1 on the F(4x4) kernel: full tile columns there + the last pixel column as a strip
-                  convolution (GLASS_W43_RAGGED=0: a whole extra tile column, as in rounds 2-3)
+      ragged      maps of width 4 k + 1 on the F(4x4) kernel: "tiles" (the default) = the full tile columns + the last pixel column
+                  as paired strip tiles of the SAME launch; True (GLASS_W43_RAGGED=strip) = what True has meant since round 4 and
+                  what the split-K and F(2x2) body forms still do: the full tile columns, then the last pixel column as a strip
+                  convolution - a second launch (kept selectable: the A/B partner of "tiles"); False (GLASS_W43_RAGGED=0): a whole
+                  extra tile column, as in rounds 2-3
       rnn         the recurrent encoder: (directions, RoI groups) a workgroup of the one-launch-per-layer BiLSTM kernel
                   interleaves - "1x1" (default: shortest chain, 3 % off the one-step-at-a-time latency), "2x1", "2x2",
                   "persistent" = the library's default - or "steps" (GLASS_RNN=steps: one launch per time step,
@@ -151,7 +161,7 @@ class Routing:
 
     def __init__(self, precision: Optional[str] = None, winograd: Optional[bool] = None, f43: Optional[bool] = None, pw=None,
                  h16: Optional[bool] = None, local_stem: Optional[bool] = None, stem: Optional[bool] = None,
-                 ragged: Optional[bool] = None, pooled_fusion: Optional[bool] = None, rnn=None,
+                 ragged=None, pooled_fusion: Optional[bool] = None, rnn=None,
                  splitk: Optional[bool] = None, small_grid: Optional[bool] = None, split: Optional[int] = None):
         e = os.environ.get
         self.precision = precision or e("GLASS_CONV_PRECISION", "fp32")
@@ -163,7 +173,7 @@ class Routing:
         self.h16 = (e("GLASS_CONV_H16", "1") != "0") if h16 is None else bool(h16)
         self.local_stem = (e("GLASS_LOCAL_STEM", "1") != "0") if local_stem is None else bool(local_stem)
         self.stem = (e("GLASS_BACKBONE_STEM", "1") != "0") if stem is None else bool(stem)
-        self.ragged = (e("GLASS_W43_RAGGED", "1") != "0") if ragged is None else bool(ragged)
+        self.ragged = _parse_ragged(e("GLASS_W43_RAGGED", "tiles") if ragged is None else ragged)
         self.pooled_fusion = (e("GLASS_POOLED_FUSION", "1") != "0") if pooled_fusion is None else bool(pooled_fusion)
         self.rnn = _parse_rnn(e("GLASS_RNN", "1x1")) if rnn is None else _parse_rnn(rnn)
         self.splitk = (e("GLASS_SPLITK", "1") != "0") if splitk is None else bool(splitk)
@@ -180,6 +190,7 @@ class Routing:
             raise GlassLibraryError(f"unknown conv precision {r.precision!r}")
         r.split = _parse_split(r.split)
         r.rnn = _parse_rnn(r.rnn)
+        r.ragged = _parse_ragged(r.ragged)
         return r
 
     @property
@@ -229,7 +240,7 @@ def act_dtype(w=None) -> torch.dtype:
 
 
 def last_conv_path() -> str:
-    """'pointwise' (conv1x1_pw_f32), 'winograd43' (conv3x3_wino43_f32; 'winograd43r': its full tile columns + the last pixel column as a strip convolution), 'fused_stem', 'winograd128' / 'winograd' (conv3x3_wino128_f32 / conv3x3_wino_f32), 'direct', 'direct_fp16' (fp32 template, fp16 operands) or 'packed_fp16' (conv_h16_kernel): which kernel
+    """'pointwise' (conv1x1_pw_f32), 'winograd43' (conv3x3_wino43_f32; 'winograd43r': a map of width 4 k + 1 - its full tile columns + the last pixel column as paired strip tiles of the same launch, or as a strip convolution), 'fused_stem', 'winograd128' / 'winograd' (conv3x3_wino128_f32 / conv3x3_wino_f32), 'direct', 'direct_fp16' (fp32 template, fp16 operands) or 'packed_fp16' (conv_h16_kernel): which kernel
     the most recent conv2d_nhwc call OF THIS HOST THREAD launched (bench/profiling aid)."""
     return getattr(_TLS, "last_path", "direct")
 
@@ -447,10 +458,12 @@ def _probe_desc(Cout: int, KH: int, KW: int, Cin: int) -> ConvDesc:
     return ConvDesc(1, 16, 16, Cin, Cout, KH, KW, 1, 1, ph, pw, 16 + 2 * ph - KH + 1, 16 + 2 * pw - KW + 1, Cin, Cout, 0, 1, 0, 0, 0)
 
 
-def pack_kinds(Cout: int, KH: int, KW: int, Cin: int, precision: str, stride=1, ragged: bool = False, split: int = 0) -> list:
+def pack_kinds(Cout: int, KH: int, KW: int, Cin: int, precision: str, stride=1, ragged: bool = False, split: int = 0,
+               strip: bool = True) -> list:
     """which packed forms a [Cout,KH,KW,Cin] weight can be asked for under `precision` (the routing of conv2d_nhwc);
     "all": every form the layer supports (micro-benchmarks that force kernels across precisions).  `stride` != 1 rules the
-    Winograd forms out (stride-2 3x3 layers were carrying 52/9 of their size in packs no launch could take)."""
+    Winograd forms out (stride-2 3x3 layers were carrying 52/9 of their size in packs no launch could take).
+    `strip` False: the routing the layer is loaded for cannot reach the last-column strip convolution (see needs_strip_pack)."""
     if precision == "all":
         return pack_kinds(Cout, KH, KW, Cin, "fp32", stride, ragged, split=9) + pack_kinds(Cout, KH, KW, Cin, "fp16", stride)
     L, d = lib(), _probe_desc(Cout, KH, KW, Cin)
@@ -461,7 +474,7 @@ def pack_kinds(Cout: int, KH: int, KW: int, Cin: int, precision: str, stride=1, 
                 kinds.append(False)
             if L.glass_winograd43_supported(ctypes.byref(d)):
                 kinds.append(True)
-                if ragged and (2 * Cin) % 32 == 0:
+                if ragged and strip and (2 * Cin) % 32 == 0:
                     kinds.append("col1")     # the layer meets maps of width 4 k + 1 (caller's hint): strip weights of the last column
         if KH == 1 and KW == 1 and L.glass_pointwise_supported(ctypes.byref(d)):
             kinds.append("pw")
@@ -472,11 +485,20 @@ def pack_kinds(Cout: int, KH: int, KW: int, Cin: int, precision: str, stride=1, 
     return kinds
 
 
+def needs_strip_pack(rt: Routing) -> bool:
+    """can a layer loaded under `rt` still launch the last-column strip convolution on a map of width 4 k + 1?  The F(4x4) kernel
+    computes that column itself (glass_conv3x3_winograd43_ragged_nhwc); the strip remains behind the small-grid rules only - the
+    F(2x2) body form and the split-K body form, both for few RoIs - or everywhere under ragged = True, the two-launch form.
+    Otherwise no launch can ask for the "col1" pack."""
+    return bool(rt.ragged and rt.winograd and (rt.small_grid or rt.ragged != "tiles"))
+
+
 def prepare_conv_weights(w: torch.Tensor, precision: Optional[str] = None, stride=1, ragged: bool = False) -> ConvWeight:
     """w [Cout,KH,KW,Cin] (or [Nout,K] for a linear layer) fp32 on the device -> ConvWeight with every packed form its layer
     can be routed to under `precision` (default: the enclosing packing_for(), else the raw-tensor default precision).
     `stride`: the layer's stride when the caller knows it (a stride-2 3x3 layer needs no Winograd form); `ragged`: the layer
-    runs on maps of width 4 k + 1 (the local extractor's 16 x 33 maps) and wants the last-column strip weights.  Load-time plumbing:
+    runs on maps of width 4 k + 1 (the local extractor's 16 x 33 maps) and wants the last-column strip weights where its routing
+    can still launch the strip (needs_strip_pack).  Load-time plumbing:
     ~10 pack kernels per MB of weights, once per model."""
     if isinstance(w, ConvWeight):
         return w
@@ -487,7 +509,8 @@ def prepare_conv_weights(w: torch.Tensor, precision: Optional[str] = None, strid
     precision = precision or (load.precision if load is not None else _DEFAULT.precision)
     Cout, KH, KW, Cin = w.shape
     if w.is_cuda:
-        for kind in pack_kinds(Cout, KH, KW, Cin, precision, stride, ragged, split=(load.split if load is not None else _DEFAULT.split)):
+        rt = load if load is not None else _DEFAULT
+        for kind in pack_kinds(Cout, KH, KW, Cin, precision, stride, ragged, split=rt.split, strip=needs_strip_pack(rt)):
             cw.packs[kind] = winograd_pack(w, kind)
         if cw.packs and load is None:
             torch.cuda.current_stream().synchronize()      # other streams (pipelined steps) may launch with it next
@@ -593,7 +616,12 @@ def plan_conv(d: ConvDesc, rt: Routing, *, x_dtype: torch.dtype, out_dtype: torc
     # so that no launch of the model path ever packs; raw tensors (tests, scripts) get them packed for the launch.
     can_strip = (rt.ragged and three and W % 2 == 1 and W >= 5 and (2 * Cin) % 32 == 0 and y_cstride == 1 and ldx == Cin and
                  res_mode in (0, 1) and N * H * W * ldx > 0 and (packs is None or "col1" in packs))
-    ragged = can_body = can_strip and W % 4 == 1
+    can_body = can_strip and W % 4 == 1
+    # width 4 k + 1 on the F(4x4) kernel needs neither the strip weights nor dense rows: the last column runs as paired strip
+    # tiles of the same launch (glass_conv3x3_winograd43_ragged_nhwc) on the layer's F(4x4) pack
+    can_ragged = (rt.ragged == "tiles" and three and W % 4 == 1 and y_cstride == 1 and res_mode in (0, 1) and N * H * W * ldx > 0 and
+                  bool(L.glass_winograd43_ragged_supported(dp)))
+    ragged = can_ragged or can_body
     f43 = forced == "f43" or (forced is None and rt.f43 and use_wino and three and _use_f43(N, H, W, Cout, Cin, ragged))
     f22_body = forced == "f22r"                     # forced: F(2x2) on the full tile columns + the last-column strip (tests)
     if f22_body and not can_strip:
@@ -619,11 +647,16 @@ def plan_conv(d: ConvDesc, rt: Routing, *, x_dtype: torch.dtype, out_dtype: torc
             if (t_alt is None or t_sk < (0.8 if body else 0.85) * t_alt) and L.glass_winograd43_splitk_supported(dp, sl):
                 return ConvPlan("winograd43k", "glass_conv3x3_winograd43_splitk_nhwc", True, int(body), sl, strip=body)
     if use_wino and f43 and three and L.glass_winograd43_supported(dp):
+        if ragged and can_ragged:
+            # width 4 k + 1: the F(4x4) kernel on the k full tile columns and, in the same launch, one strip tile per tile row
+            # and PAIR of images for the last pixel column - 34 instead of 36 tiles per 16 x 33 map, e.g. 1088 instead of 1152
+            # workgroups at 256 RoIs.  (The path name - and with it bench.py's FLOP meter, which prices the last column as
+            # 3 x 2 direct taps - is the one the body + strip form had.)
+            return ConvPlan("winograd43r", "glass_conv3x3_winograd43_ragged_nhwc", True)
         if ragged:
-            # width 4 k + 1: the F(4x4) kernel on the k full tile columns - 32 instead of 36 tiles per 16 x 33 map, and e.g.
-            # 1024 instead of 1152 workgroups = 4 instead of 4.5 rounds on 256 CUs - and the last pixel column as a KH = 3,
-            # KW = 1 convolution over the last two input columns seen as 2*Cin channels (x, y and the residual re-viewed as
-            # [N,H,1,W*ld] rows with a channel offset; no copy)
+            # ... where the ragged entry refuses the layer (an operand within one image of 1 GiB): the full tile columns, then
+            # the last pixel column as a KH = 3, KW = 1 convolution over the last two input columns seen as 2*Cin channels
+            # (x, y and the residual re-viewed as [N,H,1,W*ld] rows with a channel offset; no copy)
             return ConvPlan("winograd43r", "glass_conv3x3_winograd43_body_nhwc", True, strip=True)
         return ConvPlan("winograd43", "glass_conv3x3_winograd43_nhwc", True)
     if forced == "f43":

@@ -141,6 +141,15 @@ int glass_conv3x3_winograd43_nhwc(const glass_conv_desc* d, const float* x, cons
  * channels = (kw, cin), see glass_amd/ops/native.py).  Same descriptor (the TRUE H, W), epilogue and errors.          */
 int glass_conv3x3_winograd43_body_nhwc(const glass_conv_desc* d, const float* x, const float* u_packed, const float* bias,
                                        const float* residual, float* y, glass_stream_t stream);
+/* ... and widths 4 k + 1 >= 5 in ONE launch: the full tile columns as glass_conv3x3_winograd43_body_nhwc, followed in the same
+ * grid by ceil(N / 2) * ceil(H / 4) paired strip tiles that compute the last pixel column of two images each (patch columns
+ * W-2, W-1 of image 2 q and of image 2 q + 1 around zero columns; output columns 0 and 3 of the tile are the two images' column
+ * W-1) - same packed weights, same arithmetic as every other column, every pixel of y written once, nothing else touched.
+ * glass_winograd43_ragged_supported: glass_winograd43_supported, W % 4 == 1, W >= 5 and each operand's span plus one image
+ * below 1 GiB (the second image is reached through the column part of the split offsets).                                   */
+int glass_winograd43_ragged_supported(const glass_conv_desc* d);
+int glass_conv3x3_winograd43_ragged_nhwc(const glass_conv_desc* d, const float* x, const float* u_packed, const float* bias,
+                                         const float* residual, float* y, glass_stream_t stream);
 /* Split-K form of the F(4x4,3x3) entry (ABI 7; wide shape only: Cout % 128 == 0, Cin % 32 == 0): `splits` (2..32, dividing Cin / 32)
  * k-slices of the layer run as independent workgroups, each writes the raw partial output of its slice to
  * workspace[slice][N H W][Cout] (>= glass_winograd43_splitk_workspace_bytes, 16-byte aligned), and an ordered reduction adds the
