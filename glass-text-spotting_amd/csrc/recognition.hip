@@ -1,5 +1,5 @@
 // Per-RoI recognition kernels: global-to-local fusion attention (softmax pooling + channel MLP),
-// the BiLSTM recurrence and the greedy attention-GRU decoder.
+// the BiLSTM recurrence, the greedy attention-GRU decoder and its beam search.
 //
 // All three are independent across RoIs.  The fusion attention is one workgroup per RoI.  The two recurrences are
 // ONE LAUNCH PER DEPENDENT STEP (T launches of lstm_step_kernel per layer; dec_fc_att_kernel + dec_gru_kernel per
@@ -631,5 +631,328 @@ extern "C" int glass_attention_decode_step(const float* x, const float* xproj, c
   p.logits = logits_out;
   fc_att(h_out, 0, 0);                           // logits = fc(h_out) * temperature, probs = softmax(logits)
   GLASS_CHECK_LAUNCH("glass_attention_decode_step");
+  return GLASS_OK;
+}
+
+// ================================================================== beam search (AttentionRecognitionHead.beam_search)
+// The whole search of reference prediction_aster.py:101-222 behind one ABI call: per step dec_gru_kernel on the B*k state rows
+// and beam_step_kernel (one workgroup per batch item), then one beam_backtrack_kernel (one wavefront per item).  No host
+// synchronisation, no read-back; x / xproj stay [B,T,D]: an item's rows are read once per step and serve its k beams.
+//   workspace: hsel [B*k,D] (states gathered by predecessor = the GRU's h_prev) | hraw [B*k,D] (the GRU's output) |
+//              inp [B*k,2D] | score, predecessor and symbol tables [B,L,k] each (predecessors are beam slots 0..k-1)
+// Selection rule (torch.topk leaves ties open): candidates ordered by score descending, then by flat index beam*C + class
+// ascending; -inf candidates last, in index order.
+constexpr int BEAM_KMAX = 16;
+constexpr int BEAM_LMAX = 64;
+
+struct BeamParams {
+  float* sc; int* pr; int* sy;      // decision tables [B][L][k]
+  float* hsel;                      // [B*k][D]
+  int k, L, eos;
+};
+
+// step == -1: only the attention part with h = 0, y = 0 ([GO]) -> inp rows of step 0; step >= 0: fc + log-softmax + running
+// score + top-k of the item's k*C candidates -> tables[step], then (unless it is the last step) predecessor gather of the
+// states and the attention / embedding part for step + 1.  The fc / sEmbed mat-vecs, the energies and the two reductions are
+// dec_fc_att_kernel's, element for element, so the logits are those of glass_attention_decode_step on inflated inputs.
+// KB = k rounded up to 1, 2, 4, 8 or 16 (rows >= k are zero and never written out).
+template <int KB>
+__global__ __launch_bounds__(256) void beam_step_kernel(DecParams p, BeamParams bp, const float* __restrict__ hraw, int step) {
+  __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
+  __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
+  __shared__ float cand[KB][DEC_CMAX];
+  __shared__ float energy[KB][DEC_TMAX];
+  __shared__ float run[KB];
+  __shared__ int ysel[KB], psel[KB];
+  __shared__ float wbest[2][4];
+  __shared__ int wbesti[2][4];
+  const int u = threadIdx.x, lane = u & 63, wave = u >> 6;
+  const int b = blockIdx.x;
+  const int T = p.T, C = p.C, k = bp.k, L = bp.L;
+  const long row0 = (long)b * k;
+#pragma unroll
+  for (int r = 0; r < KB; ++r) h[r][u] = (step >= 0 && r < k) ? hraw[(row0 + r) * DEC_D + u] : 0.f;
+  if (u < KB) {
+    ysel[u] = 0;
+    psel[u] = 0;
+    float rs = -INFINITY;
+    if (u < k) {
+      if (step <= 0) rs = u == 0 ? 0.f : -INFINITY;
+      else {
+        const long i = ((long)b * L + (step - 1)) * k + u;
+        rs = bp.sy[i] == bp.eos ? -INFINITY : bp.sc[i];
+      }
+    }
+    run[u] = rs;
+  }
+  __syncthreads();
+  if (step >= 0) {
+    // ---- logits = fc(h) * temperature
+    if (u < C) {
+      float acc[1][KB];
+#pragma unroll
+      for (int r = 0; r < KB; ++r) acc[0][r] = p.fcB[u];
+      stream_matvec<1, KB, 16>(reinterpret_cast<const float4*>(p.fcW), C, 0, u, DEC_D / 4, &h[0][0], DEC_D, acc);
+#pragma unroll
+      for (int r = 0; r < KB; ++r) cand[r][u] = acc[0][r] * p.temperature;
+    }
+    __syncthreads();
+    // ---- candidate score = running score + log-softmax (x - max - log(sum exp(x - max))), wavefront per beam
+    for (int r = wave; r < k; r += 4) {
+      float v[DEC_CMAX / 64];
+      float m = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < DEC_CMAX / 64; ++i) {
+        const int cidx = lane + 64 * i;
+        v[i] = cidx < C ? cand[r][cidx] : -INFINITY;
+        m = fmaxf(m, v[i]);
+      }
+      m = wave_max(m);
+      float s = 0.f;
+#pragma unroll
+      for (int i = 0; i < DEC_CMAX / 64; ++i) s += (lane + 64 * i) < C ? expf(v[i] - m) : 0.f;
+      s = wave_sum(s);
+      const float ls = logf(s), rs = run[r];
+#pragma unroll
+      for (int i = 0; i < DEC_CMAX / 64; ++i) {
+        const int cidx = lane + 64 * i;
+        if (cidx < C) cand[r][cidx] = rs + ((v[i] - m) - ls);
+      }
+    }
+    __syncthreads();
+    // ---- top k of the k*C candidates: k rounds of (max score, then min flat index); thread u owns class u of every beam
+    unsigned taken = 0u;
+    for (int j = 0; j < k; ++j) {
+      float best = -INFINITY;
+      int besti = 0x7fffffff;
+      if (u < C) {
+#pragma unroll
+        for (int r = 0; r < KB; ++r) {
+          if (r < k && !((taken >> r) & 1u)) {
+            const float v = cand[r][u];
+            if (besti == 0x7fffffff || v > best) { best = v; besti = r * C + u; }
+          }
+        }
+      }
+      wave_argmax_first(best, besti);
+      if (lane == 0) { wbest[j & 1][wave] = best; wbesti[j & 1][wave] = besti; }
+      __syncthreads();
+      float gb = wbest[j & 1][0];
+      int gi = wbesti[j & 1][0];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) {
+        const float vb = wbest[j & 1][w];
+        const int vi = wbesti[j & 1][w];
+        if (vi != 0x7fffffff && (gi == 0x7fffffff || vb > gb || (vb == gb && vi < gi))) { gb = vb; gi = vi; }
+      }
+      // k <= C: a candidate is always left and gi is a real index - unless the logits hold NaN (outside the contract):
+      // the tables must still hold valid slots and classes, they index memory in the later steps and in the back-tracking
+      if (gi == 0x7fffffff) gi = j;
+      const int beam = gi / C, cls = gi - beam * C;
+      if (u == cls) taken |= 1u << beam;
+      if (u == 0) {
+        const long i = ((long)b * L + step) * k + j;
+        bp.sc[i] = gb; bp.pr[i] = beam; bp.sy[i] = cls;
+        ysel[j] = cls; psel[j] = beam;
+      }
+    }
+    if (step + 1 >= L) return;
+    __syncthreads();
+    // ---- states follow their predecessors (in place: column u of every row passes through registers)
+    float hv[KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) hv[r] = r < k ? h[psel[r]][u] : 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < KB; ++r) {
+      h[r][u] = hv[r];
+      if (r < k) bp.hsel[(row0 + r) * DEC_D + u] = hv[r];
+    }
+    __syncthreads();
+  }
+  // ---- sProj = sEmbed(h)
+  {
+    float acc[1][KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) acc[0][r] = p.sB[u];
+    stream_matvec<1, KB, 16>(reinterpret_cast<const float4*>(p.sW), DEC_D, 0, u, DEC_D / 4, &h[0][0], DEC_D, acc);
+#pragma unroll
+    for (int r = 0; r < KB; ++r) sproj[r][u] = acc[0][r];
+  }
+  __syncthreads();
+  // ---- energies e[r][t] = wEmbed(tanh(sProj[r] + xProj[t])): one xProj row per wavefront pass, shared by the k beams
+  {
+    const float4 ww = *reinterpret_cast<const float4*>(p.wW + lane * 4);
+    const float wb = p.wB[0];
+    for (int t = wave; t < T; t += 4) {
+      const float4 xp = *reinterpret_cast<const float4*>(p.xproj + ((long)b * T + t) * DEC_D + lane * 4);
+      for (int r = 0; r < k; ++r) {
+        const float4 sp = *reinterpret_cast<const float4*>(&sproj[r][lane * 4]);
+        float s = ww.x * tanh_fast(sp.x + xp.x) + ww.y * tanh_fast(sp.y + xp.y) + ww.z * tanh_fast(sp.z + xp.z) +
+                  ww.w * tanh_fast(sp.w + xp.w);
+        s = wave_sum(s);
+        if (lane == 0) energy[r][t] = s + wb;
+      }
+    }
+  }
+  __syncthreads();
+  for (int r = wave; r < k; r += 4) {
+    const float v = lane < T ? energy[r][lane] : -INFINITY;
+    const float m = wave_max(v);
+    const float e = lane < T ? expf(v - m) : 0.f;
+    const float s = wave_sum(e);
+    if (lane < T) energy[r][lane] = e / s;
+  }
+  __syncthreads();
+  // ---- inp = [embedding(y) | context = alpha . x]: one x row per t, shared by the k beams
+  {
+    float s[KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) s[r] = 0.f;
+    const float* xr = p.x + (long)b * T * DEC_D + u;
+    for (int t = 0; t < T; ++t) {
+      const float xv = xr[(long)t * DEC_D];
+#pragma unroll
+      for (int r = 0; r < KB; ++r)
+        if (r < k) s[r] += energy[r][t] * xv;
+    }
+#pragma unroll
+    for (int r = 0; r < KB; ++r) {
+      if (r < k) {
+        float* ip = p.inp + (row0 + r) * (2 * DEC_D);
+        ip[u] = p.emb[(long)ysel[r] * DEC_D + u];
+        ip[DEC_D + u] = s[r];
+      }
+    }
+  }
+}
+
+// rank of slot `i` among v[0..k) by value descending, then slot ascending (-inf entries last, in slot order)
+__device__ __forceinline__ int beam_rank(const float* v, int k, int i) {
+  int rank = 0;
+  const float vi = v[i];
+  for (int j = 0; j < k; ++j) rank += (v[j] > vi || (v[j] == vi && j < i)) ? 1 : 0;
+  return rank;
+}
+
+// The reference's back-tracking (prediction_aster.py:161-222), one wavefront per item, lane r = result slot r: the last
+// step's beams sorted, the backward pass with "an ended sequence replaces the worst slot" (slot k - found % k - 1, <eos>
+// entries of a step taken from the highest beam down), the final re-sort.  Path rows of the best hypothesis: row t < length
+// holds exp(score_t - score_{t-1}) at its symbol along the hypothesis's own ancestor chain, every other entry zero.
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(BeamParams bp, int C, int* __restrict__ out_sym,
+                                                            float* __restrict__ out_sc, int* __restrict__ out_len,
+                                                            float* __restrict__ out_path) {
+  __shared__ int p_sym[BEAM_LMAX][BEAM_KMAX];
+  __shared__ int p_idx[BEAM_LMAX][BEAM_KMAX];
+  __shared__ float s_s[BEAM_KMAX];
+  __shared__ int s_len[BEAM_KMAX], s_ord[BEAM_KMAX];
+  const int b = blockIdx.x, lane = threadIdx.x, k = bp.k, L = bp.L;
+  // the item's decision tables, staged once: the backward pass reads them in a dependent chain
+  __shared__ float sc[BEAM_LMAX * BEAM_KMAX];
+  __shared__ int pr[BEAM_LMAX * BEAM_KMAX], sy[BEAM_LMAX * BEAM_KMAX];
+  for (int i = lane; i < L * k; i += 64) {
+    sc[i] = bp.sc[(long)b * L * k + i];
+    pr[i] = bp.pr[(long)b * L * k + i];
+    sy[i] = bp.sy[(long)b * L * k + i];
+  }
+  __syncthreads();
+  if (lane < k) s_s[lane] = sc[(L - 1) * k + lane];
+  __syncthreads();
+  if (lane < k) s_ord[beam_rank(s_s, k, lane)] = lane;
+  __syncthreads();
+  float s = 0.f;
+  int tp = 0, len = L, found = 0;
+  if (lane < k) { tp = s_ord[lane]; s = s_s[tp]; }
+  for (int t = L - 1; t >= 0; --t) {
+    int cur = 0, idx = 0;
+    if (lane < k) { idx = tp; cur = sy[t * k + tp]; tp = pr[t * k + tp]; }
+    for (int j = k - 1; j >= 0; --j) {
+      const int symj = sy[t * k + j];
+      if (symj == bp.eos) {
+        const int res = k - (found % k) - 1;
+        ++found;
+        if (lane == res) { tp = pr[t * k + j]; cur = symj; idx = j; s = sc[t * k + j]; len = t + 1; }
+      }
+    }
+    if (lane < k) { p_sym[t][lane] = cur; p_idx[t][lane] = idx; }
+  }
+  __syncthreads();
+  if (lane < k) { s_s[lane] = s; s_len[lane] = len; }
+  __syncthreads();
+  if (lane < k) s_ord[beam_rank(s_s, k, lane)] = lane;
+  __syncthreads();
+  for (int i = lane; i < k * L; i += 64) {
+    const int r = i / L, t = i - r * L;
+    out_sym[((long)b * k + r) * L + t] = p_sym[t][s_ord[r]];
+  }
+  if (lane < k) {
+    out_sc[(long)b * k + lane] = s_s[s_ord[lane]];
+    out_len[(long)b * k + lane] = s_len[s_ord[lane]];
+  }
+  if (out_path == nullptr) return;
+  float* op = out_path + (long)b * L * C;
+  for (int i = lane; i < L * C; i += 64) op[i] = 0.f;
+  __syncthreads();
+  const int slot = s_ord[0];
+  if (lane < s_len[slot] && s_s[slot] > -INFINITY) {
+    const int t = lane;
+    const float cur = sc[t * k + p_idx[t][slot]];
+    const float prev = t > 0 ? sc[(t - 1) * k + p_idx[t - 1][slot]] : 0.f;
+    op[(long)t * C + p_sym[t][slot]] = expf(cur - prev);
+  }
+}
+
+extern "C" int64_t glass_beam_search_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  (void)T; (void)C;
+  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
+  const size_t rows = (size_t)B * k;
+  return (int64_t)(rows * D * 4 * sizeof(float) + (size_t)B * max_len * k * (2 * sizeof(int) + sizeof(float)));
+}
+
+extern "C" int glass_beam_search(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
+                                 int C, int max_len, int eos, int* out_symbols, float* out_scores, int* out_lengths,
+                                 float* out_path_probs, void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
+  GLASS_CHECK_ARG(D == DEC_D && T > 0 && T <= DEC_TMAX && C > 0 && C <= DEC_CMAX && k >= 1 && k <= BEAM_KMAX && k <= C &&
+                      max_len >= 1 && max_len <= BEAM_LMAX && B >= 0,
+                  "glass_beam_search: needs D=256, 1<=T<=64, 1<=C<=256, 1<=k<=16, k<=C, 1<=max_len<=64, B>=0 "
+                  "(got B=%d k=%d T=%d D=%d C=%d max_len=%d)", B, k, T, D, C, max_len);
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && workspace, "glass_beam_search: null pointer");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_workspace_bytes(B, k, T, D, C, max_len),
+                  "glass_beam_search: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_beam_search_workspace_bytes(B, k, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * k;
+  DecParams p;
+  p.x = x; p.xproj = xproj; p.sW = w->sW; p.sB = w->sB; p.wW = w->wW; p.wB = w->wB; p.emb = w->emb; p.w_ih = w->w_ih;
+  p.w_hh = w->w_hh; p.b_ih = w->b_ih; p.b_hh = w->b_hh; p.fcW = w->fcW; p.fcB = w->fcB; p.temperature = w->temperature;
+  p.R = (int)rows; p.T = T; p.C = C; p.max_len = max_len; p.out = nullptr; p.pred = nullptr; p.yprev = nullptr; p.logits = nullptr;
+  float* ws = static_cast<float*>(workspace);
+  float* hsel = ws;
+  float* hraw = ws + rows * D;
+  p.h0 = hsel; p.h1 = hraw; p.inp = ws + rows * D * 2;
+  BeamParams bp;
+  bp.sc = ws + rows * D * 4;
+  bp.pr = reinterpret_cast<int*>(bp.sc + (size_t)B * max_len * k);
+  bp.sy = bp.pr + (size_t)B * max_len * k;
+  bp.hsel = hsel; bp.k = k; bp.L = max_len; bp.eos = eos;
+  hipError_t e = hipMemsetAsync(hsel, 0, rows * D * sizeof(float), s);           // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_beam_search: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B), gg(cdiv((long)rows, GRU_RB), DEC_D / GRU_UB);
+  auto beam_step = [&](int step) {
+    if (k == 1) hipLaunchKernelGGL(beam_step_kernel<1>, gb, dim3(256), 0, s, p, bp, hraw, step);
+    else if (k == 2) hipLaunchKernelGGL(beam_step_kernel<2>, gb, dim3(256), 0, s, p, bp, hraw, step);
+    else if (k <= 4) hipLaunchKernelGGL(beam_step_kernel<4>, gb, dim3(256), 0, s, p, bp, hraw, step);
+    else if (k <= 8) hipLaunchKernelGGL(beam_step_kernel<8>, gb, dim3(256), 0, s, p, bp, hraw, step);
+    else hipLaunchKernelGGL(beam_step_kernel<16>, gb, dim3(256), 0, s, p, bp, hraw, step);
+  };
+  beam_step(-1);                                                                  // attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    hipLaunchKernelGGL(dec_gru_kernel, gg, dim3(256), 0, s, p, hsel, hraw);
+    beam_step(step);
+  }
+  GLASS_CHECK_LAUNCH("glass_beam_search");
+  hipLaunchKernelGGL(beam_backtrack_kernel, gb, dim3(64), 0, s, bp, C, out_symbols, out_scores, out_lengths, out_path_probs);
+  GLASS_CHECK_LAUNCH("glass_beam_search(backtrack)");
   return GLASS_OK;
 }

@@ -134,6 +134,10 @@ def add_e2e_config(cfg: CN) -> None:
     blk = _recognizer_block("", "CNN_V1_2", "BiLSTMBlockV2", "ASTER_V2")
     blk.update({"POOLER_TYPE": "ROIAlignRotated", "NORM": "BN", "POOLER_SAMPLING_RATIO": 0,
                 "CONV_DIM": 256, "SAMPLING_RATIO": 0})
+    # MI355X build only (not a reference key): 0 = greedy decoding, the reference's inference path; k >= 1 = beam search of
+    # width k on the device (ASTER_V2.beam_decode, glass_beam_search; k <= 16) - `pred_text_prob` then holds the best
+    # hypothesis as path rows (one non-zero entry per step: the step's conditional probability at the emitted symbol)
+    blk["BEAM_WIDTH"] = 0
     cfg.MODEL.merge_from_other_cfg({"ROI_RECOGNIZER_HEAD": blk})
 
 

@@ -8,10 +8,15 @@ prediction_aster.py:63-99 (greedy sampling, eos index 0, pre-zeroed [R,26,97] ou
 the batch-global early break), AttentionUnit :247-266, DecoderUnit :291-302.
 xEmbed(x) is recomputed at every step by the reference; it is step-invariant, so it is one
 MFMA GEMM here.
+
+Beam search (`AttentionRecognitionHead.beam_search`, prediction_aster.py:101-222, unused by the reference's inference path):
+`ASTER_V2.beam_search` is the readable host statement (one decoder-step call per step, the search in torch and Python);
+`ASTER_V2.beam_decode` is the same search as ONE ABI call on the device (glass_beam_search), which
+`MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH` switches the recognizer head to.
 """
 from __future__ import annotations
 
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -22,6 +27,14 @@ from ...ops import native as K
 from ...utils.registry import Registry
 
 RECOGNIZER_DECODER_REGISTRY = Registry("RECOGNIZER_DECODER")
+
+
+class BeamResult(NamedTuple):
+    """`ASTER_V2.beam_decode`: device tensors, hypotheses in final (best first) order"""
+    symbols: torch.Tensor                   # int32 [B, k, L]
+    scores: torch.Tensor                    # float32 [B, k] sum of log-probabilities; -inf = no such hypothesis
+    lengths: torch.Tensor                   # int32 [B, k] t + 1 for a sequence that ended at step t, else L
+    path_probs: Optional[torch.Tensor]      # float32 [B, L, C] rows of the best hypothesis, or None
 
 
 def build_recognizer_decoderv2(cfg, input_shape):
@@ -130,6 +143,19 @@ class ASTER_V2(InferenceModule):
         p = [step.index_select(0, re_sorted_idx).view(B, k, -1) for step in reversed(p)]
         p = torch.cat(p, -1)[:, 0, :]
         return p.to(dev_), s[:, 0].to(dev_)
+
+    def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False) -> "BeamResult":
+        """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
+        synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
+        `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
+        decoder's `pred_text_prob` read unchanged (arg-max = symbol, max = conditional probability of the step, zero rows
+        from the hypothesis's length on).  Ties are ordered by flat candidate index, which `torch.topk` in `beam_search`
+        leaves open."""
+        x = x.contiguous()
+        B, T, D = x.shape
+        xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x      # empty batch: empty results
+        out = K.beam_search(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos), path_probs=path_probs)
+        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None)
 
     def forward(self, features: torch.Tensor, labels=None, roi_image: Optional[torch.Tensor] = None,
                 num_images: int = 1, rnn=None, status=None) -> torch.Tensor:

@@ -33,6 +33,14 @@ class RecognizerRCNNHeadV3(InferenceModule):
         self.max_word_length = cfg.MODEL.ROI_RECOGNIZER_HEAD.MAX_WORD_LENGTH
         self.class_ind = cfg.MODEL.ROI_RECOGNIZER_HEAD.CLASS_IND
         self.text_encoder = TextEncoder(cfg)
+        # MI355X build only: 0 = greedy decoding (the reference's path), k >= 1 = beam search of width k on the device
+        self.beam_width = int(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "BEAM_WIDTH", 0))
+        if not 0 <= self.beam_width <= 16:
+            raise ValueError(f"MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH must be in 0..16 (got {self.beam_width})")
+        # a hypothesis ends where the word post-processing stops reading: at the text encoder's stop symbol ('[s]'), so the
+        # word score the consumers of `pred_text_prob` compute from the path rows is exp(score of the best hypothesis)
+        ch = self.text_encoder.character
+        self.beam_eos = ch.index("[s]") if "[s]" in ch else 0
 
     def import_weights(self, sd, device, prefix: str) -> None:
         self.backbone.import_weights(sd, device, prefix + "backbone.")
@@ -43,7 +51,7 @@ class RecognizerRCNNHeadV3(InferenceModule):
     rnn_giveups = 0
 
     def forward_nhwc(self, x: torch.Tensor, roi_image: torch.Tensor, num_images: int, guard=None) -> torch.Tensor:
-        """x [R,8,32,256] fused features -> probabilities [R,26,97].
+        """x [R,8,32,256] fused features -> probabilities [R,26,97] (BEAM_WIDTH >= 1: the best hypothesis's path rows).
         `guard` (ops.native.HandoffGuard): the one-launch BiLSTM / decoder kernels report a hand-off that gave up into
         `guard.status`, and `guard.retry` re-runs encoder + decoder of THIS call on the step kernels - the caller resolves the
         guard at its next host read-back (GeneralizedRCNN._postprocess_batched_g: the surviving-count read).  Without a guard
@@ -57,6 +65,8 @@ class RecognizerRCNNHeadV3(InferenceModule):
 
         def run(rnn, status):
             enc = self.encoder.forward_nhwc(f, rnn=rnn, status=status)
+            if self.beam_width > 0:         # the search has no in-kernel hand-off: only the encoder is guarded
+                return self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True).path_probs
             return self.decoder(enc, roi_image=roi_image, num_images=num_images, rnn=rnn, status=status)
         if self.rnn_override == "steps":
             return run("steps", None)

@@ -1303,6 +1303,34 @@ def attention_decode_step(x: torch.Tensor, xproj: torch.Tensor, weights: dict, h
     return logits, probs, h_out
 
 
+def beam_search(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int, eos: int,
+                path_probs: bool = False):
+    """the whole beam search on the device (glass_beam_search; reference AttentionRecognitionHead.beam_search): x, xproj
+    [B,T,D] un-inflated -> (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k][, path rows [B,max_len,C] of the
+    best hypothesis]), all k hypotheses in final order.  No host synchronisation; limits are checked by the library."""
+    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj")
+    if xproj.shape != x.shape or xproj.device != x.device:
+        raise GlassLibraryError(f"beam_search: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
+    B, T, D = x.shape
+    k, C, L = int(beam_width), int(num_classes), int(max_len)
+    dev = x.device
+    symbols = torch.empty((B, max(k, 0), max(L, 0)), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    lengths = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    path = torch.empty((B, max(L, 0), max(C, 0)), dtype=torch.float32, device=dev) if path_probs else None
+    w = DecoderWeights()
+    for n in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB"):
+        setattr(w, n, _dev(_f32c(weights[n], n)))
+    w.temperature = float(weights["temperature"])
+    nbytes = int(lib().glass_beam_search_workspace_bytes(B, k, T, D, C, L))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(lib().glass_beam_search(c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), B, k, T, D, C, L, int(eos),
+                                  c_void_p(_dev(symbols)), c_void_p(_dev(scores)), c_void_p(_dev(lengths)),
+                                  c_void_p(_dev(path)) if path is not None else None, c_void_p(_dev(ws)),
+                                  ctypes.c_int64(nbytes), c_void_p(stream_handle())), "glass_beam_search")
+    return (symbols, scores, lengths, path) if path_probs else (symbols, scores, lengths)
+
+
 def detections_finalize(boxes: torch.Tensor, scores: torch.Tensor, orient: Optional[torch.Tensor],
                         text: Optional[torch.Tensor], counts: torch.Tensor, roi_start: Optional[torch.Tensor],
                         scale_xy: torch.Tensor, out_hw: torch.Tensor, min_box_dim: float, do_filter_small: bool):

@@ -529,6 +529,30 @@ int glass_attention_decode_step(const float* x, const float* xproj, const glass_
                                 const float* h_in, const int* y_prev, float* h_out, float* logits_out, float* probs_out,
                                 void* workspace, int64_t workspace_bytes, glass_stream_t stream);
 
+/* The WHOLE beam search of AttentionRecognitionHead.beam_search (prediction_aster.py:101-222) behind one call: all max_len
+ * steps and the back-tracking are enqueued here, with no host synchronisation and no read-back.  x, xproj [B,T,D] are the
+ * UN-inflated tensors: an item's rows are read once per step and shared by its k beams (nothing of size B*k*T*D exists).
+ * Per step: the GRU cell of glass_attention_decode on the B*k state rows, then one workgroup per item does fc, fp32
+ * log-softmax (x - max - log(sum exp(x - max))), adds the running scores, selects the top k of the k*C candidates, records
+ * score / predecessor / symbol, freezes a beam that emitted `eos` at -inf, gathers the predecessors' states and forms the next
+ * GRU input (additive attention + embedding); the logits are those of glass_attention_decode_step on inflated inputs.
+ * Selection rule (also of the two sorts of the back-tracking): score descending, then flat index beam*C + class (slot)
+ * ascending; -inf entries last, in index order.  NaN logits are outside the contract.
+ * Back-tracking, one wavefront per item: the reference's algorithm (:161-222) - last-step beams sorted, backward pass in
+ * which a sequence that ended at step t replaces slot k - (found % k) - 1, final re-sort.  All k hypotheses in final order:
+ *   out_symbols [B,k,max_len] ints, out_scores [B,k], out_lengths [B,k] ints (t+1 for a sequence that ended at step t, else
+ *   max_len; symbols at and after position `length` are whatever the slot held before, as in the reference);
+ *   out_path_probs [B,max_len,C] or null - the best hypothesis as rows a consumer of the greedy decoder's probabilities can
+ *   read: row t < length is zero except exp(score_t - score_{t-1}) (score_{-1} = 0, scores along the hypothesis's ancestor
+ *   chain) at symbols[t]; rows t >= length, and every row of a hypothesis whose score is -inf, are zero.
+ * Needs D == 256, 1 <= T <= 64, 1 <= C <= 256, 1 <= k <= 16, k <= C, 1 <= max_len <= 64; B == 0 returns GLASS_OK.
+ * `workspace` (16-byte aligned) >= glass_beam_search_workspace_bytes().  2 * max_len + 2 launches, ordinary grids with bounded
+ * loops; no float atomics - results are bit-identical from run to run.                                                      */
+int64_t glass_beam_search_workspace_bytes(int B, int k, int T, int D, int C, int max_len);
+int glass_beam_search(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D, int C,
+                      int max_len, int eos, int* out_symbols, float* out_scores, int* out_lengths, float* out_path_probs,
+                      void* workspace, int64_t workspace_bytes, glass_stream_t stream);
+
 /* ------------------------------------------------------------------ lexicon matching (evaluation)
  * find_match_word, un-weighted branch (glass/evaluation/lexicon_utils.py:4-28): for each query q, the word of lexicon segment
  * q_segment[q] at the smallest unit-cost Levenshtein distance, first strict minimum in file order.  Symbols are bytes, both
