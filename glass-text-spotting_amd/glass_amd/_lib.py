@@ -40,6 +40,7 @@ EXPORTS = [
     "glass_rrc_sweep_workspace_bytes", "glass_rrc_sweep",
     "glass_mask_windows", "glass_mask_rings_workspace_bytes", "glass_mask_rings_count", "glass_mask_rings_write",
     "glass_ring_check_tasks", "glass_ring_check",
+    "glass_resize_pil_workspace_bytes", "glass_resize_u8_pil", "glass_resize_u8_pil_into_batch",
 ]
 
 
@@ -151,6 +152,11 @@ def lib() -> ctypes.CDLL:
         L.glass_postprocess_words_dense_workspace_bytes.restype = ctypes.c_int64
         L.glass_mask_rings_workspace_bytes.restype = ctypes.c_int64
         L.glass_ring_check_tasks.restype = ctypes.c_int64
+        L.glass_resize_pil_workspace_bytes.restype = ctypes.c_int64
+        L.glass_resize_u8_pil.restype = ctypes.c_int
+        L.glass_resize_u8_pil.argtypes = [_p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _l, _p, _i, _i, _p]
+        L.glass_resize_u8_pil_into_batch.restype = ctypes.c_int
+        L.glass_resize_u8_pil_into_batch.argtypes = [_p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _l, _i, _i, _p, _p, _i, _p, _i, _i, _i, _p]
         _LIB = L
     return _LIB
 

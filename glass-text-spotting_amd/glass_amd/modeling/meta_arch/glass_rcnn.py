@@ -5,7 +5,9 @@ Mirrors reference glass/modeling/meta_arch/glass_rcnn.py:13-128 (`GlassRCNN.from
 stock `GeneralizedRCNN` (configs/glass_pretrain.yaml:40), the same flow with d2's
 `detector_postprocess` [d2-recall].  Call convention is the reference's:
 `model(batched_inputs: list[{'image': Tensor[3,H,W] float 0..255, 'height', 'width'}])
- -> list[{'instances': Instances}]`.
+ -> list[{'instances': Instances}]`.  Next to 'image' an input may be the raw form of `data.DatasetMapper(fused=True)`,
+`{'image_u8': uint8 [H,W,3] on the device, 'resize': (Ho, Wo)}`: preprocess_image then does the mapper's PIL-bilinear
+resize itself, fused with the normalisation (ops.native.pil_resize_into_batch) - the same bits as the 'image' form.
 
 Batches: the reference effectively runs one image per call; a batch here gives,
 per image, exactly what the reference gives when run image by image.
@@ -78,16 +80,27 @@ class GeneralizedRCNN(InferenceModule):
         return self.load_state_dict(load_checkpoint_file(path))
 
     # ------------------------------------------------------------------ pipeline
+    @staticmethod
+    def input_size(x: Dict):
+        """(h, w) the model sees: of "image", or the "resize" target of the raw form {"image_u8", "resize"}"""
+        if "image" in x:
+            return int(x["image"].shape[-2]), int(x["image"].shape[-1])
+        return int(x["resize"][0]), int(x["resize"][1])
+
     def preprocess_image(self, batched_inputs: List[Dict], into: Optional[torch.Tensor] = None) -> ImageList:
         """normalise + zero-pad to a multiple of 32 into one NHWC4 batch (glass_rcnn.py:82).  `into`: an existing
         [N,Hp,Wp,4] buffer to fill (the static input of a captured graph)."""
-        imgs = [x["image"] for x in batched_inputs]
-        sizes = [(int(im.shape[-2]), int(im.shape[-1])) for im in imgs]
+        sizes = [self.input_size(x) for x in batched_inputs]
         Hp, Wp = ImageList.padded_shape(sizes, self.backbone.size_divisibility)
-        batch = into if into is not None else torch.empty((len(imgs), Hp, Wp, 4), dtype=torch.float32, device=self._device)
-        assert tuple(batch.shape) == (len(imgs), Hp, Wp, 4)
-        for n, im in enumerate(imgs):
-            im = im.to(self._device)
+        batch = into if into is not None else torch.empty((len(sizes), Hp, Wp, 4), dtype=torch.float32, device=self._device)
+        assert tuple(batch.shape) == (len(sizes), Hp, Wp, 4)
+        for n, x in enumerate(batched_inputs):
+            if "image" not in x:
+                # the raw form of data.DatasetMapper(fused=True): PIL-bilinear resize, normalise and pad in one launch pair
+                K.pil_resize_into_batch(x["image_u8"].to(self._device).contiguous(), x["resize"], self.pixel_mean,
+                                        self.pixel_std, batch, n)
+                continue
+            im = x["image"].to(self._device)
             if im.dtype != torch.float32:
                 im = im.float()
             K.preprocess_image(im.contiguous(), self.pixel_mean, self.pixel_std, batch, n)
@@ -130,7 +143,7 @@ class GeneralizedRCNN(InferenceModule):
 
     def _inference_body_g(self, batched_inputs, detected_instances, do_postprocess, override_boxes):
         if detected_instances is None:
-            sizes = [(int(x["image"].shape[-2]), int(x["image"].shape[-1])) for x in batched_inputs]
+            sizes = [self.input_size(x) for x in batched_inputs]
             hw_new = K.upload(sizes, torch.int32, self._device)
             images = self.preprocess_image(batched_inputs)
             t = self._trunk(images.nhwc4, hw_new)

@@ -987,6 +987,78 @@ def image_u8hwc_to_chw(img: torch.Tensor, out_hw: Tuple[int, int], flip_channels
     return out
 
 
+_PIL_TABLES: dict = {}      # (in, out, device) -> (k, bounds, ksize) on the device; a few KB each, made once per axis length
+_PIL_TABLES_LOCK = threading.Lock()
+
+
+def _pil_tables(in_size: int, out_size: int, device):
+    """device copies of data.transforms.pil_bilinear_coeffs(in, out); (None, None, 0) for an axis that keeps its size.
+    The upload is a blocking copy, so the tables are complete for whatever stream reads them later."""
+    if in_size == out_size:
+        return None, None, 0
+    key = (int(in_size), int(out_size), torch.device(device))
+    with _PIL_TABLES_LOCK:
+        hit = _PIL_TABLES.get(key)
+        if hit is None:
+            from ..data.transforms import pil_bilinear_coeffs
+            k, b = pil_bilinear_coeffs(key[0], key[1])
+            if len(_PIL_TABLES) >= 256:
+                _PIL_TABLES.clear()
+            hit = _PIL_TABLES[key] = (torch.from_numpy(np.array(k)).to(device), torch.from_numpy(np.array(b)).to(device), int(k.shape[1]))
+    return hit
+
+
+def _pil_resize_args(img: torch.Tensor, out_hw: Tuple[int, int]):
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or not img.is_contiguous() or img.dim() != 3 or img.shape[2] != 3:
+        raise GlassLibraryError("image must be contiguous uint8 HWC with 3 channels")
+    _dev(img, "image")
+    H, W, _ = img.shape
+    Ho, Wo = int(out_hw[0]), int(out_hw[1])
+    kx, bx, nx = _pil_tables(W, Wo, img.device)
+    ky, by, ny = _pil_tables(H, Ho, img.device)
+    ptr = lambda t: c_void_p(t.data_ptr() if t is not None else None)       # noqa: E731
+    return H, W, Ho, Wo, (ptr(kx), ptr(bx), nx, ptr(ky), ptr(by), ny), (kx, bx, ky, by)
+
+
+def pil_resize_workspace(H: int, W: int, Ho: int, Wo: int, device) -> Optional[torch.Tensor]:
+    nbytes = int(lib().glass_resize_pil_workspace_bytes(int(H), int(W), int(Ho), int(Wo)))
+    return torch.empty((nbytes,), dtype=torch.uint8, device=device) if nbytes else None
+
+
+def pil_resize_u8(img: torch.Tensor, out_hw: Tuple[int, int], workspace: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """PIL.Image.resize((Wo, Ho), BILINEAR) of a device uint8 HWC image, byte for byte -> uint8 [Ho,Wo,3]
+    (data.transforms.pil_resize_u8_host is the same in numpy).  `workspace`: a uint8 buffer of
+    glass_resize_pil_workspace_bytes to reuse; allocated here by default."""
+    H, W, Ho, Wo, tables, _keep = _pil_resize_args(img, out_hw)
+    out = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=img.device)
+    ws = workspace if workspace is not None else pil_resize_workspace(H, W, Ho, Wo, img.device)
+    check(lib().glass_resize_u8_pil(c_void_p(_dev(img)), H, W, *tables, c_void_p(_dev(ws) if ws is not None else None),
+                                    ws.numel() * ws.element_size() if ws is not None else 0, c_void_p(_dev(out)), Ho, Wo,
+                                    c_void_p(stream_handle())), "glass_resize_u8_pil")
+    return out
+
+
+def pil_resize_into_batch(img: torch.Tensor, out_hw: Tuple[int, int], mean: Sequence[float], std: Sequence[float],
+                          batch: torch.Tensor, n: int, flip_channels: bool = False,
+                          workspace: Optional[torch.Tensor] = None) -> None:
+    """pil_resize_u8 + (x - mean)/std -> slot n of the zero-padded NHWC4 batch [N,Hp,Wp,4] in one launch pair: bit-equal to
+    preprocess_image(pil_resize_u8(img, out_hw).permute(2, 0, 1).float(), ...), channels 0 and 2 swapped first if
+    `flip_channels`."""
+    H, W, Ho, Wo, tables, _keep = _pil_resize_args(img, out_hw)
+    _f32c(batch, "batch")
+    N, Hp, Wp, four = batch.shape
+    assert four == 4
+    if not 0 <= int(n) < N:
+        raise GlassLibraryError(f"slot {n} outside a batch of {N}")
+    m = (c_float * 3)(*[float(v) for v in mean])
+    s = (c_float * 3)(*[float(v) for v in std])
+    ws = workspace if workspace is not None else pil_resize_workspace(H, W, Ho, Wo, img.device)
+    check(lib().glass_resize_u8_pil_into_batch(c_void_p(_dev(img)), H, W, *tables, c_void_p(_dev(ws) if ws is not None else None),
+                                               ws.numel() * ws.element_size() if ws is not None else 0, Ho, Wo, m, s, int(flip_channels),
+                                               c_void_p(_dev(batch)), int(n), Hp, Wp, c_void_p(stream_handle())),
+          "glass_resize_u8_pil_into_batch")
+
+
 def roi_align_rotated(feats: List[torch.Tensor], scales: Sequence[float], boxes: torch.Tensor, batch_idx: torch.Tensor,
                       out_size: Tuple[int, int], sampling_ratio: int, channels: Optional[int] = None,
                       out: Optional[torch.Tensor] = None, out_coff: int = 0, out_cstride: int = 1, up2: bool = False) -> torch.Tensor:

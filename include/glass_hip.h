@@ -706,6 +706,29 @@ int64_t glass_ring_check_tasks(int n_points_of_ring);
 int glass_ring_check(const int* pts, int64_t n_points, const int* ring_off, int n_rings, const int64_t* task_off, int64_t n_tasks,
                      int* verdict, int64_t* area2, glass_stream_t stream);
 
+/* ------------------------------------------------------------------ PIL bilinear resize (test-time ResizeShortestEdge)
+ * PIL.Image.resize((Wo, Ho), BILINEAR) of a uint8 HWC image [H,W,3], byte for byte: what detectron2's ResizeShortestEdge
+ * does to a uint8 image in DatasetMapper(cfg, is_train=False) (glass/data/dataset_mapper.py:45,85 [d2-recall]).  Two
+ * separable passes, horizontal first into a uint8 image [H,Wo,3], each output sample
+ *   clamp((2^21 + sum_t k[o][t] * pixel[first + t]) >> 22, 0, 255)
+ * with the host-made tables of an axis (glass_amd/data/transforms.py pil_bilinear_coeffs): k int32 [out][ksize] and
+ * bounds int32 [out][2] = (first tap, tap count <= ksize).  A pass whose axis keeps its size is skipped and its tables
+ * may be null.  The kernels clamp every table row to the axis, so no table can make them read outside the image.
+ * glass_resize_pil_workspace_bytes: H * Wo * 3 for the intermediate image, 0 when the width does not change.
+ * glass_resize_u8_pil: dst uint8 HWC [Ho,Wo,3].  Uses the workspace only when both passes run; both skipped is a copy.
+ * glass_resize_u8_pil_into_batch: the vertical pass stores ((float)u8 - mean[c]) / std[c] (the operation order of
+ *   glass_preprocess_image), with channels 0 and 2 swapped first if flip_channels, into slot `n` of the float NHWC4 batch
+ *   [N,Hp,Wp,4] (16-byte aligned; Ho <= Hp, Wo <= Wp); channel 3 and every pixel with h >= Ho or w >= Wo are 0.  Bit-equal
+ *   to glass_resize_u8_pil followed by a cast and glass_preprocess_image.  Two launches (one when the width is kept);
+ *   needs the workspace whenever the width changes.                                                                      */
+int64_t glass_resize_pil_workspace_bytes(int H, int W, int Ho, int Wo);
+int glass_resize_u8_pil(const uint8_t* src, int H, int W, const int* kx, const int* bx, int ksize_x, const int* ky, const int* by,
+                        int ksize_y, void* workspace, int64_t workspace_bytes, uint8_t* dst, int Ho, int Wo, glass_stream_t stream);
+int glass_resize_u8_pil_into_batch(const uint8_t* src, int H, int W, const int* kx, const int* bx, int ksize_x, const int* ky,
+                                   const int* by, int ksize_y, void* workspace, int64_t workspace_bytes, int Ho, int Wo,
+                                   const float* mean3, const float* std3, int flip_channels, float* batch_nhwc4, int n, int Hp,
+                                   int Wp, glass_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
