@@ -651,6 +651,104 @@ struct BeamParams {
   int k, L, eos;
 };
 
+// ---- pieces of one decoder step on the KB rows of ONE item (beam_step_kernel: its k beams; forced_step_kernel: its n given
+// sequences), called by all 256 threads of the workgroup; u = threadIdx.x.  They are dec_fc_att_kernel's arithmetic, element for
+// element.
+// logits = fc(h) * temperature -> cand[r][0..C)
+template <int KB>
+__device__ __forceinline__ void rows_fc(const DecParams& p, int C, int u, const float (*h)[DEC_D], float (*cand)[DEC_CMAX]) {
+  if (u < C) {
+    float acc[1][KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) acc[0][r] = p.fcB[u];
+    stream_matvec<1, KB, 16>(reinterpret_cast<const float4*>(p.fcW), C, 0, u, DEC_D / 4, &h[0][0], DEC_D, acc);
+#pragma unroll
+    for (int r = 0; r < KB; ++r) cand[r][u] = acc[0][r] * p.temperature;
+  }
+}
+
+// log-softmax of one row by one wavefront: lane owns classes lane + 64 i -> v[i] = x (-inf beyond C), m = max, returns
+// log(sum exp(x - m)); the log-softmax of class lane + 64 i is (v[i] - m) - ls
+__device__ __forceinline__ float row_lsm(const float* row, int C, int lane, float (&v)[DEC_CMAX / 64], float& m) {
+  m = -INFINITY;
+#pragma unroll
+  for (int i = 0; i < DEC_CMAX / 64; ++i) {
+    const int cidx = lane + 64 * i;
+    v[i] = cidx < C ? row[cidx] : -INFINITY;
+    m = fmaxf(m, v[i]);
+  }
+  m = wave_max(m);
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < DEC_CMAX / 64; ++i) s += (lane + 64 * i) < C ? expf(v[i] - m) : 0.f;
+  s = wave_sum(s);
+  return logf(s);
+}
+
+// additive attention of the item's k rows with the states in h, and the GRU input of the next step:
+// inp[row0 + r] = [embedding(ysel[r]) | alpha[r] . x[b]] for r < k.  x / xproj rows of item b are read once and serve all k rows.
+// The caller has synchronised after writing h and ysel.
+template <int KB>
+__device__ __forceinline__ void rows_attend(const DecParams& p, int b, int k, long row0, int u, const float (*h)[DEC_D],
+                                            float (*sproj)[DEC_D], float (*energy)[DEC_TMAX], const int* ysel) {
+  const int lane = u & 63, wave = u >> 6, T = p.T;
+  // ---- sProj = sEmbed(h)
+  {
+    float acc[1][KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) acc[0][r] = p.sB[u];
+    stream_matvec<1, KB, 16>(reinterpret_cast<const float4*>(p.sW), DEC_D, 0, u, DEC_D / 4, &h[0][0], DEC_D, acc);
+#pragma unroll
+    for (int r = 0; r < KB; ++r) sproj[r][u] = acc[0][r];
+  }
+  __syncthreads();
+  // ---- energies e[r][t] = wEmbed(tanh(sProj[r] + xProj[t])): one xProj row per wavefront pass, shared by the k rows
+  {
+    const float4 ww = *reinterpret_cast<const float4*>(p.wW + lane * 4);
+    const float wb = p.wB[0];
+    for (int t = wave; t < T; t += 4) {
+      const float4 xp = *reinterpret_cast<const float4*>(p.xproj + ((long)b * T + t) * DEC_D + lane * 4);
+      for (int r = 0; r < k; ++r) {
+        const float4 sp = *reinterpret_cast<const float4*>(&sproj[r][lane * 4]);
+        float s = ww.x * tanh_fast(sp.x + xp.x) + ww.y * tanh_fast(sp.y + xp.y) + ww.z * tanh_fast(sp.z + xp.z) +
+                  ww.w * tanh_fast(sp.w + xp.w);
+        s = wave_sum(s);
+        if (lane == 0) energy[r][t] = s + wb;
+      }
+    }
+  }
+  __syncthreads();
+  for (int r = wave; r < k; r += 4) {
+    const float v = lane < T ? energy[r][lane] : -INFINITY;
+    const float m = wave_max(v);
+    const float e = lane < T ? expf(v - m) : 0.f;
+    const float s = wave_sum(e);
+    if (lane < T) energy[r][lane] = e / s;
+  }
+  __syncthreads();
+  // ---- inp = [embedding(y) | context = alpha . x]: one x row per t, shared by the k rows
+  {
+    float s[KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) s[r] = 0.f;
+    const float* xr = p.x + (long)b * T * DEC_D + u;
+    for (int t = 0; t < T; ++t) {
+      const float xv = xr[(long)t * DEC_D];
+#pragma unroll
+      for (int r = 0; r < KB; ++r)
+        if (r < k) s[r] += energy[r][t] * xv;
+    }
+#pragma unroll
+    for (int r = 0; r < KB; ++r) {
+      if (r < k) {
+        float* ip = p.inp + (row0 + r) * (2 * DEC_D);
+        ip[u] = p.emb[(long)ysel[r] * DEC_D + u];
+        ip[DEC_D + u] = s[r];
+      }
+    }
+  }
+}
+
 // step == -1: only the attention part with h = 0, y = 0 ([GO]) -> inp rows of step 0; step >= 0: fc + log-softmax + running
 // score + top-k of the item's k*C candidates -> tables[step], then (unless it is the last step) predecessor gather of the
 // states and the attention / embedding part for step + 1.  The fc / sEmbed mat-vecs, the energies and the two reductions are
@@ -668,7 +766,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(DecParams p, BeamParams 
   __shared__ int wbesti[2][4];
   const int u = threadIdx.x, lane = u & 63, wave = u >> 6;
   const int b = blockIdx.x;
-  const int T = p.T, C = p.C, k = bp.k, L = bp.L;
+  const int C = p.C, k = bp.k, L = bp.L;
   const long row0 = (long)b * k;
 #pragma unroll
   for (int r = 0; r < KB; ++r) h[r][u] = (step >= 0 && r < k) ? hraw[(row0 + r) * DEC_D + u] : 0.f;
@@ -688,31 +786,13 @@ __global__ __launch_bounds__(256) void beam_step_kernel(DecParams p, BeamParams 
   __syncthreads();
   if (step >= 0) {
     // ---- logits = fc(h) * temperature
-    if (u < C) {
-      float acc[1][KB];
-#pragma unroll
-      for (int r = 0; r < KB; ++r) acc[0][r] = p.fcB[u];
-      stream_matvec<1, KB, 16>(reinterpret_cast<const float4*>(p.fcW), C, 0, u, DEC_D / 4, &h[0][0], DEC_D, acc);
-#pragma unroll
-      for (int r = 0; r < KB; ++r) cand[r][u] = acc[0][r] * p.temperature;
-    }
+    rows_fc<KB>(p, C, u, h, cand);
     __syncthreads();
     // ---- candidate score = running score + log-softmax (x - max - log(sum exp(x - max))), wavefront per beam
     for (int r = wave; r < k; r += 4) {
       float v[DEC_CMAX / 64];
-      float m = -INFINITY;
-#pragma unroll
-      for (int i = 0; i < DEC_CMAX / 64; ++i) {
-        const int cidx = lane + 64 * i;
-        v[i] = cidx < C ? cand[r][cidx] : -INFINITY;
-        m = fmaxf(m, v[i]);
-      }
-      m = wave_max(m);
-      float s = 0.f;
-#pragma unroll
-      for (int i = 0; i < DEC_CMAX / 64; ++i) s += (lane + 64 * i) < C ? expf(v[i] - m) : 0.f;
-      s = wave_sum(s);
-      const float ls = logf(s), rs = run[r];
+      float m;
+      const float ls = row_lsm(cand[r], C, lane, v, m), rs = run[r];
 #pragma unroll
       for (int i = 0; i < DEC_CMAX / 64; ++i) {
         const int cidx = lane + 64 * i;
@@ -770,61 +850,7 @@ __global__ __launch_bounds__(256) void beam_step_kernel(DecParams p, BeamParams 
     }
     __syncthreads();
   }
-  // ---- sProj = sEmbed(h)
-  {
-    float acc[1][KB];
-#pragma unroll
-    for (int r = 0; r < KB; ++r) acc[0][r] = p.sB[u];
-    stream_matvec<1, KB, 16>(reinterpret_cast<const float4*>(p.sW), DEC_D, 0, u, DEC_D / 4, &h[0][0], DEC_D, acc);
-#pragma unroll
-    for (int r = 0; r < KB; ++r) sproj[r][u] = acc[0][r];
-  }
-  __syncthreads();
-  // ---- energies e[r][t] = wEmbed(tanh(sProj[r] + xProj[t])): one xProj row per wavefront pass, shared by the k beams
-  {
-    const float4 ww = *reinterpret_cast<const float4*>(p.wW + lane * 4);
-    const float wb = p.wB[0];
-    for (int t = wave; t < T; t += 4) {
-      const float4 xp = *reinterpret_cast<const float4*>(p.xproj + ((long)b * T + t) * DEC_D + lane * 4);
-      for (int r = 0; r < k; ++r) {
-        const float4 sp = *reinterpret_cast<const float4*>(&sproj[r][lane * 4]);
-        float s = ww.x * tanh_fast(sp.x + xp.x) + ww.y * tanh_fast(sp.y + xp.y) + ww.z * tanh_fast(sp.z + xp.z) +
-                  ww.w * tanh_fast(sp.w + xp.w);
-        s = wave_sum(s);
-        if (lane == 0) energy[r][t] = s + wb;
-      }
-    }
-  }
-  __syncthreads();
-  for (int r = wave; r < k; r += 4) {
-    const float v = lane < T ? energy[r][lane] : -INFINITY;
-    const float m = wave_max(v);
-    const float e = lane < T ? expf(v - m) : 0.f;
-    const float s = wave_sum(e);
-    if (lane < T) energy[r][lane] = e / s;
-  }
-  __syncthreads();
-  // ---- inp = [embedding(y) | context = alpha . x]: one x row per t, shared by the k beams
-  {
-    float s[KB];
-#pragma unroll
-    for (int r = 0; r < KB; ++r) s[r] = 0.f;
-    const float* xr = p.x + (long)b * T * DEC_D + u;
-    for (int t = 0; t < T; ++t) {
-      const float xv = xr[(long)t * DEC_D];
-#pragma unroll
-      for (int r = 0; r < KB; ++r)
-        if (r < k) s[r] += energy[r][t] * xv;
-    }
-#pragma unroll
-    for (int r = 0; r < KB; ++r) {
-      if (r < k) {
-        float* ip = p.inp + (row0 + r) * (2 * DEC_D);
-        ip[u] = p.emb[(long)ysel[r] * DEC_D + u];
-        ip[DEC_D + u] = s[r];
-      }
-    }
-  }
+  rows_attend<KB>(p, b, k, row0, u, h, sproj, energy, ysel);
 }
 
 // rank of slot `i` among v[0..k) by value descending, then slot ascending (-inf entries last, in slot order)
@@ -954,5 +980,170 @@ extern "C" int glass_beam_search(const float* x, const float* xproj, const glass
   GLASS_CHECK_LAUNCH("glass_beam_search");
   hipLaunchKernelGGL(beam_backtrack_kernel, gb, dim3(64), 0, s, bp, C, out_symbols, out_scores, out_lengths, out_path_probs);
   GLASS_CHECK_LAUNCH("glass_beam_search(backtrack)");
+  return GLASS_OK;
+}
+
+// ================================================================== forced decoding (AttentionRecognitionHead.forward)
+// The decoder with the emitted symbols GIVEN (reference prediction_aster.py:33-60, teacher forcing): n sequences per item
+// that share the item's x / xproj rows - a word to score, the k hypotheses of a beam search, lexicon candidates.  Per step
+// dec_gru_kernel on the B*n state rows (ping-pong h0 / h1) and forced_step_kernel (one workgroup per item): fc, log-softmax,
+// the records of the step, then attention + embedding of the given symbol for the next step.  No host synchronisation.
+//   workspace: h0 [B*n,D] | h1 [B*n,D] | inp [B*n,2D] | effective length, bad-symbol flag [B*n] each
+// A sequence is computed for t < its effective length; the GRU still runs on every row (rows past their length carry
+// finite junk that is never written out).  A workgroup whose n sequences have all ended only writes the step's zeros.
+struct ForcedParams {
+  const int* targets;               // [B][n][L]
+  const int* lengths;               // [B][n] or null
+  float* step_logp;                 // [B][n][L]
+  float* scores;                    // [B][n]: the running score between the launches, the result after the last one
+  int* out_len;                     // [B][n]
+  float* probs;                     // [B][n][L][C] or null
+  float* logits;                    // [B][n][L][C] or null
+  int* elen;                        // workspace [B*n]: number of steps computed
+  int* bad;                         // workspace [B*n]: 1 = the sequence stopped at a symbol outside [0, C)
+  int n, L, eos;
+};
+
+// step == -1: effective lengths from `lengths` or the first <eos>, scores = 0, and the attention part with h = 0, y = 0 ([GO])
+// -> inp rows of step 0; step >= 0: fc + log-softmax of the GRU's output rows -> the records of row `step` (zeros for a
+// sequence that has ended), then - if any sequence goes on - attention with y = targets[step] -> inp rows of step + 1.
+// A symbol is used as an index (embedding row, log-softmax entry) only after the range check of the step -1 launch, which ends a
+// sequence AT the first symbol outside [0, C) with score -inf; the index is clamped once more where it is used.
+template <int KB>
+__global__ __launch_bounds__(256) void forced_step_kernel(DecParams p, ForcedParams fp, const float* __restrict__ hraw, int step) {
+  __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
+  __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
+  __shared__ float cand[KB][DEC_CMAX];
+  __shared__ float energy[KB][DEC_TMAX];
+  __shared__ int ycur[KB], ysel[KB], slen[KB], sbad[KB];
+  const int u = threadIdx.x, lane = u & 63, wave = u >> 6;
+  const int b = blockIdx.x;
+  const int C = p.C, n = fp.n, L = fp.L;
+  const long row0 = (long)b * n;
+  if (u < KB) {
+    int len = 0, bad = 0, y = 0;
+    if (u < n) {
+      const long row = row0 + u;
+      const int* tg = fp.targets + row * L;
+      if (step < 0) {
+        const bool given = fp.lengths != nullptr;
+        const int lim = given ? min(max(fp.lengths[row], 0), L) : L;
+        len = lim;
+        for (int t = 0; t < lim; ++t) {
+          const int sym = tg[t];
+          if (sym < 0 || sym >= C) { len = t; bad = 1; break; }
+          if (!given && sym == fp.eos) { len = t + 1; break; }
+        }
+        fp.elen[row] = len;
+        fp.bad[row] = bad;
+        fp.out_len[row] = len;
+        fp.scores[row] = (bad && len == 0) ? -INFINITY : 0.f;
+      } else {
+        len = fp.elen[row];
+        bad = fp.bad[row];
+        if (step < len) y = min(max(tg[step], 0), C - 1);
+      }
+    }
+    ycur[u] = y;
+    ysel[u] = (step >= 0 && step + 1 < len) ? y : 0;
+    slen[u] = len;
+    sbad[u] = bad;
+  }
+  __syncthreads();
+  if (step >= 0) {
+    bool now = false, next = false;
+    for (int r = 0; r < n; ++r) { now = now || step < slen[r]; next = next || step + 1 < slen[r]; }
+    if (now) {                                                  // uniform over the workgroup
+#pragma unroll
+      for (int r = 0; r < KB; ++r) h[r][u] = r < n ? hraw[(row0 + r) * DEC_D + u] : 0.f;
+      __syncthreads();
+      rows_fc<KB>(p, C, u, h, cand);
+      __syncthreads();
+    }
+    // ---- the records of row `step`, wavefront per sequence
+    for (int r = wave; r < n; r += 4) {
+      const long rec = (row0 + r) * L + step;
+      const bool live = step < slen[r];
+      float v[DEC_CMAX / 64];
+      float m = 0.f, ls = 0.f;
+      if (live) ls = row_lsm(cand[r], C, lane, v, m);
+#pragma unroll
+      for (int i = 0; i < DEC_CMAX / 64; ++i) {
+        const int cidx = lane + 64 * i;
+        if (cidx < C) {
+          const float l = live ? (v[i] - m) - ls : 0.f;
+          if (fp.probs != nullptr) fp.probs[rec * C + cidx] = live ? expf(l) : 0.f;
+          if (fp.logits != nullptr) fp.logits[rec * C + cidx] = live ? v[i] : 0.f;
+          if (live && cidx == ycur[r]) {
+            fp.step_logp[rec] = l;
+            const float sc = fp.scores[row0 + r] + l;           // fl32(score_{t-1} + step_logp[t]), in step order
+            fp.scores[row0 + r] = (sbad[r] && step + 1 == slen[r]) ? -INFINITY : sc;
+          }
+        }
+      }
+      if (!live && lane == 0) fp.step_logp[rec] = 0.f;
+    }
+    if (!next || step + 1 >= L) return;
+    __syncthreads();
+  } else {
+#pragma unroll
+    for (int r = 0; r < KB; ++r) h[r][u] = 0.f;
+    __syncthreads();
+  }
+  rows_attend<KB>(p, b, n, row0, u, h, sproj, energy, ysel);
+}
+
+extern "C" int64_t glass_forced_decode_workspace_bytes(int B, int n, int T, int D, int C, int max_len) {
+  (void)T; (void)C;
+  if (B <= 0 || n <= 0 || D <= 0 || max_len <= 0) return 0;
+  const size_t rows = (size_t)B * n;
+  return (int64_t)(rows * D * 4 * sizeof(float) + rows * 2 * sizeof(int));
+}
+
+extern "C" int glass_forced_decode(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T, int D,
+                                   int C, int max_len, int eos, const int* targets, const int* lengths, float* out_step_logp,
+                                   float* out_scores, int* out_lengths, float* out_probs, float* out_logits, void* workspace,
+                                   int64_t workspace_bytes, glass_stream_t stream) {
+  GLASS_CHECK_ARG(D == DEC_D && T > 0 && T <= DEC_TMAX && C > 0 && C <= DEC_CMAX && n >= 1 && n <= BEAM_KMAX && max_len >= 1 &&
+                      max_len <= BEAM_LMAX && B >= 0,
+                  "glass_forced_decode: needs D=256, 1<=T<=64, 1<=C<=256, 1<=n<=16, 1<=max_len<=64, B>=0 "
+                  "(got B=%d n=%d T=%d D=%d C=%d max_len=%d)", B, n, T, D, C, max_len);
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && targets && out_step_logp && out_scores && out_lengths && workspace,
+                  "glass_forced_decode: null pointer");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len),
+                  "glass_forced_decode: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * n;
+  DecParams p;
+  p.x = x; p.xproj = xproj; p.sW = w->sW; p.sB = w->sB; p.wW = w->wW; p.wB = w->wB; p.emb = w->emb; p.w_ih = w->w_ih;
+  p.w_hh = w->w_hh; p.b_ih = w->b_ih; p.b_hh = w->b_hh; p.fcW = w->fcW; p.fcB = w->fcB; p.temperature = w->temperature;
+  p.R = (int)rows; p.T = T; p.C = C; p.max_len = max_len; p.out = nullptr; p.pred = nullptr; p.yprev = nullptr; p.logits = nullptr;
+  float* ws = static_cast<float*>(workspace);
+  p.h0 = ws; p.h1 = ws + rows * D; p.inp = ws + rows * D * 2;
+  ForcedParams fp;
+  fp.targets = targets; fp.lengths = lengths; fp.step_logp = out_step_logp; fp.scores = out_scores; fp.out_len = out_lengths;
+  fp.probs = out_probs; fp.logits = out_logits;
+  fp.elen = reinterpret_cast<int*>(ws + rows * D * 4);
+  fp.bad = fp.elen + rows;
+  fp.n = n; fp.L = max_len; fp.eos = eos;
+  hipError_t e = hipMemsetAsync(p.h0, 0, rows * D * sizeof(float), s);           // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_forced_decode: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B), gg(cdiv((long)rows, GRU_RB), DEC_D / GRU_UB);
+  float* hb[2] = {p.h0, p.h1};
+  auto forced_step = [&](const float* hraw, int step) {
+    if (n == 1) hipLaunchKernelGGL(forced_step_kernel<1>, gb, dim3(256), 0, s, p, fp, hraw, step);
+    else if (n == 2) hipLaunchKernelGGL(forced_step_kernel<2>, gb, dim3(256), 0, s, p, fp, hraw, step);
+    else if (n <= 4) hipLaunchKernelGGL(forced_step_kernel<4>, gb, dim3(256), 0, s, p, fp, hraw, step);
+    else if (n <= 8) hipLaunchKernelGGL(forced_step_kernel<8>, gb, dim3(256), 0, s, p, fp, hraw, step);
+    else hipLaunchKernelGGL(forced_step_kernel<16>, gb, dim3(256), 0, s, p, fp, hraw, step);
+  };
+  forced_step(hb[0], -1);                                                         // lengths, and the attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    hipLaunchKernelGGL(dec_gru_kernel, gg, dim3(256), 0, s, p, hb[step & 1], hb[(step + 1) & 1]);
+    forced_step(hb[(step + 1) & 1], step);
+  }
+  GLASS_CHECK_LAUNCH("glass_forced_decode");
   return GLASS_OK;
 }

@@ -33,7 +33,7 @@ EXPORTS = [
     "glass_bilstm_persistent_workspace_bytes", "glass_bilstm_recurrence_persistent", "glass_recurrence_status", "glass_recurrence_test_hook",
     "glass_decode_persistent_supported", "glass_decode_persistent_workspace_bytes", "glass_attention_decode_persistent",
     "glass_decode_workspace_bytes", "glass_attention_decode", "glass_decode_step_workspace_bytes", "glass_attention_decode_step",
-    "glass_beam_search_workspace_bytes", "glass_beam_search",
+    "glass_beam_search_workspace_bytes", "glass_beam_search", "glass_forced_decode_workspace_bytes", "glass_forced_decode",
     "glass_lexicon_match_workspace_bytes", "glass_lexicon_match",
     "glass_lexicon_match_weighted_workspace_bytes", "glass_lexicon_match_weighted",
     "glass_rrc_pair_areas_workspace_bytes", "glass_rrc_pair_areas", "glass_rrc_match_workspace_bytes", "glass_rrc_match",
@@ -137,6 +137,7 @@ def lib() -> ctypes.CDLL:
         L.glass_decode_workspace_bytes.restype = ctypes.c_int64
         L.glass_decode_step_workspace_bytes.restype = ctypes.c_int64
         L.glass_beam_search_workspace_bytes.restype = ctypes.c_int64
+        L.glass_forced_decode_workspace_bytes.restype = ctypes.c_int64
         L.glass_conv2d_splitk_workspace_bytes.restype = ctypes.c_int64
         L.glass_winograd43_splitk_workspace_bytes.restype = ctypes.c_int64
         L.glass_lexicon_match_workspace_bytes.restype = ctypes.c_int64

@@ -138,6 +138,10 @@ def add_e2e_config(cfg: CN) -> None:
     # width k on the device (ASTER_V2.beam_decode, glass_beam_search; k <= 16) - `pred_text_prob` then holds the best
     # hypothesis as path rows (one non-zero entry per step: the step's conditional probability at the emitted symbol)
     blk["BEAM_WIDTH"] = 0
+    # MI355X build only: with BEAM_WIDTH >= 1 (ValueError otherwise), one forced replay of the best hypothesis
+    # (glass_forced_decode) adds its FULL per-step distributions as `pred_text_dist` [Ri,L,C] - what the weighted lexicon
+    # protocol reads (`character_probs`); `pred_text_prob` keeps the path rows, bit for bit
+    blk["BEAM_DISTRIBUTIONS"] = False
     cfg.MODEL.merge_from_other_cfg({"ROI_RECOGNIZER_HEAD": blk})
 
 

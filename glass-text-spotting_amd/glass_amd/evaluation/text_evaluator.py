@@ -154,6 +154,10 @@ def instances_to_coco_json(instances, file_name, text_encoder, onlyRemoveFirstLa
     boxes = (boxes_to_polygons(instances.pred_boxes.tensor.cpu().numpy()).tolist()
              if instances.has("pred_boxes") else [[]] * len(polygons))
     pred_text, scores_text, text_probs = get_instances_text(instances.pred_text_prob, text_encoder, onlyRemoveFirstLastCharacter)
+    if instances.has("pred_text_dist"):
+        # BEAM_DISTRIBUTIONS: pred_text_prob holds the beam search's path rows (one entry per step) - text and score come from
+        # them; the per-class probabilities the weighted lexicon protocol reads are the full rows of the forced replay
+        text_probs = instances.pred_text_dist.detach().cpu().numpy()
     scores_detection = instances.scores.tolist()
     results = []
     for poly, rec, st, cp, box, rbox, sd in zip(polygons, pred_text, scores_text, text_probs, boxes, rboxes, scores_detection):

@@ -101,8 +101,9 @@ class GlassRunner:
                     T = self.cfg.MODEL.ROI_RECOGNIZER_HEAD.MAX_WORD_LENGTH + 1
                     C = len(self.cfg.MODEL.ROI_RECOGNIZER_HEAD.CHARACTER_SET) + 2
                     text = torch.zeros(tuple(det.scores.shape) + (T, C), dtype=torch.float32, device=self.device)
-                res = self.post_processor.process_padded(det.boxes, det.scores, det.counts_dev, text, sc,
-                                                         [shapes[i] for i in idxs], {"orientations": det.orient})
+                # (BEAM_DISTRIBUTIONS: the full distribution rows are gathered with the survivors, like the orientations)
+                res = self.post_processor.process_padded(det.boxes, det.scores, det.counts_dev, text, sc, [shapes[i] for i in idxs],
+                                                         {"orientations": det.orient, "pred_text_dist": getattr(det, "text_dist", None)})
                 for i, r in zip(idxs, res):
                     out[i] = r
             else:

@@ -28,7 +28,7 @@ from ...ops import native as K
 from ...structures.core import ImageList, Instances, RotatedBoxes, ShapeSpec
 from ...utils.registry import ROI_HEADS_REGISTRY
 from ..backbone.resnet_fpn import as_nhwc
-from ..recognition.recognizer_head_v2 import build_recognizer_head
+from ..recognition.recognizer_head_v2 import build_recognizer_head, split_text_rows
 from ..roi_heads.box_head import build_box_head
 from ..roi_heads.rotated_fast_rcnn import RotatedFastRCNNOutputLayers
 from .fusion_modules import P2P3Fusion, build_hybrid_feature_fusion
@@ -67,6 +67,7 @@ class BatchedDetections:
         self.boxes, self.scores, self.orient = boxes, scores, orient
         self.counts_dev, self.counts_host, self.image_sizes = counts_dev, list(counts_host), list(image_sizes)
         self.text = None
+        self.text_dist = None         # BEAM_DISTRIBUTIONS: the best hypothesis's full per-step rows, laid out like `text`
         self.masks = None             # [sum counts, 1, M, M] mask probabilities (MASK_INFERENCE), or padded [N,K,M,M]
         self.kept_index = None        # [N,K] int32: index into the image's proposal list each detection came from
         self.detected = None          # with override_boxes: the box head's own detections (this object holds the overrides)
@@ -95,6 +96,12 @@ class BatchedDetections:
                 else:
                     s0 = self.roi_start_host[n]
                     r.pred_text_prob = self.text[s0:s0 + c]
+            if self.text_dist is not None:
+                if self.text_dist.dim() == 4:
+                    r.pred_text_dist = self.text_dist[n, :c]
+                else:
+                    s0 = self.roi_start_host[n]
+                    r.pred_text_dist = self.text_dist[s0:s0 + c]
             if self.masks is not None:                        # forward_with_given_boxes, :595-606
                 s0 = self.roi_start_host[n]
                 r.pred_masks = self.masks[s0:s0 + c]
@@ -191,7 +198,8 @@ class MaskRotatedRecognizerHybridHead(InferenceModule):
 
     def recognizer_branch_batched(self, img_nhwc4: torch.Tensor, feats: Dict[str, torch.Tensor], boxes: torch.Tensor,
                                   roi_image: torch.Tensor, num_images: int, return_intermediates: bool = False, guard=None):
-        """boxes [R,5], roi_image int32 [R] -> pred_text_prob [R,26,97] (R > 0).  `guard`: ops.native.HandoffGuard the caller
+        """boxes [R,5], roi_image int32 [R] -> pred_text_prob [R,26,97] (R > 0; with BEAM_DISTRIBUTIONS the pair
+        (pred_text_prob, pred_text_dist), see recognizer_head_v2.split_text_rows).  `guard`: ops.native.HandoffGuard the caller
         resolves at its next read-back (None: the recognizer head reads the hand-off status itself, synchronising)."""
         R = boxes.shape[0]
         p2, p3 = feats[self.recognizer_in_features[0]], feats[self.recognizer_in_features[1]]
@@ -310,7 +318,8 @@ class MaskRotatedRecognizerHybridHead(InferenceModule):
         # the one-launch recurrent kernels report a hand-off that gave up into det.handoff.status; the meta-arch reads it with
         # the surviving counts (its next read-back) and, if set, replaces det.text by det.handoff.retry() - the step kernels
         det.handoff = K.HandoffGuard(device)
-        det.text = self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts), guard=det.handoff)
+        det.text, det.text_dist = split_text_rows(
+            self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts), guard=det.handoff))
         if self.mask_inference:
             det.masks = self.mask_branch_batched(feats, boxes, roi_image)
         return det
@@ -325,9 +334,12 @@ class MaskRotatedRecognizerHybridHead(InferenceModule):
             roi_image = K.upload(torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32), torch.tensor(counts)), torch.int32, device)
         # reference: with no boxes the recognizer head returns the instances untouched (recognizer_head_v2.py:151)
         if self.recognizer_on and R > 0:
-            probs = self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts))
+            probs, dist = split_text_rows(self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts)))
             for p, r in zip(probs.split(counts, dim=0), results):
                 r.pred_text_prob = p
+            if dist is not None:
+                for d, r in zip(dist.split(counts, dim=0), results):
+                    r.pred_text_dist = d
         if self.mask_inference:            # forward_with_given_boxes, :594-606
             if R > 0:
                 masks = self.mask_branch_batched(feats, boxes, roi_image).split(counts, dim=0)

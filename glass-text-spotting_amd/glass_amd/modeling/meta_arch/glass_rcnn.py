@@ -30,6 +30,7 @@ from ...utils.registry import BACKBONE_REGISTRY, META_ARCH_REGISTRY, PROPOSAL_GE
 from ..backbone import resnet_fpn as _resnet_fpn  # noqa: F401  (registers the backbone builder)
 from ..backbone.resnet_fpn import as_nchw_view
 from ..fusion import recognizers_hybrid_head as _hh  # noqa: F401  (registers the ROI head)
+from ..recognition.recognizer_head_v2 import split_text_rows
 from ..proposal_generator import rotated_rpn as _rrpn  # noqa: F401  (registers RotatedRPN)
 
 
@@ -179,7 +180,7 @@ class GeneralizedRCNN(InferenceModule):
         if guard is not None:
             again = guard.resolve((yield ReadBack(guard.status))[0][0])
             if again is not None:
-                det.text = again
+                det.text, det.text_dist = split_text_rows(again)
 
     def _postprocess_batched(self, det, batched_inputs, image_sizes):
         return drive(self._postprocess_batched_g(det, batched_inputs, image_sizes))
@@ -208,6 +209,14 @@ class GeneralizedRCNN(InferenceModule):
             # the same ordered compaction for the mask rows (the kernel's "text" slot carries any per-RoI payload)
             _, _, _, om, _ = K.detections_finalize(det.boxes, det.scores, None, det.masks[:, 0].contiguous(), det.counts_dev,
                                                    roi_start, scale_xy, out_hw, float(self._min_box_dim), self._filter_small)
+
+        def finalize_dist():
+            # BEAM_DISTRIBUTIONS: the same ordered compaction for the full distribution rows, as for the mask rows
+            if getattr(det, "text_dist", None) is None:
+                return None
+            return K.detections_finalize(det.boxes, det.scores, None, det.text_dist, det.counts_dev, roi_start, scale_xy, out_hw,
+                                         float(self._min_box_dim), self._filter_small)[3]
+        od = finalize_dist()
         if guard is None:
             counts = (yield ReadBack(oc))[0].tolist()
         else:
@@ -217,12 +226,14 @@ class GeneralizedRCNN(InferenceModule):
             counts = host[0].tolist()
             again = guard.resolve(host[1][0])
             if again is not None:
-                det.text = again
+                det.text, det.text_dist = split_text_rows(again)
                 ob, os_, oo, ot, oc = K.detections_finalize(det.boxes, det.scores, det.orient, det.text, det.counts_dev, roi_start,
                                                             scale_xy, out_hw, float(self._min_box_dim), self._filter_small)
+                od = finalize_dist()
                 counts = (yield ReadBack(oc))[0].tolist()
         post = BatchedDetections(ob, os_, oo, oc, counts, out_sizes)
         post.text = ot
+        post.text_dist = od
         self.last_batch = post
         results = post.to_instances()
         if om is not None:

@@ -13,6 +13,11 @@ Beam search (`AttentionRecognitionHead.beam_search`, prediction_aster.py:101-222
 `ASTER_V2.beam_search` is the readable host statement (one decoder-step call per step, the search in torch and Python);
 `ASTER_V2.beam_decode` is the same search as ONE ABI call on the device (glass_beam_search), which
 `MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH` switches the recognizer head to.
+
+Forced decoding (`AttentionRecognitionHead.forward`, prediction_aster.py:33-60, the teacher-forced call): `ASTER_V2.score`
+runs the decoder with the emitted symbols given (glass_forced_decode, one ABI call, x / xproj not inflated) - the
+log-likelihood of a transcription; `ASTER_V2.forward(features, labels)` is the reference's surface on top of it, and
+`beam_decode(..., distributions=...)` replays the search's hypotheses for their full per-step distributions.
 """
 from __future__ import annotations
 
@@ -29,12 +34,31 @@ from ...utils.registry import Registry
 RECOGNIZER_DECODER_REGISTRY = Registry("RECOGNIZER_DECODER")
 
 
-class BeamResult(NamedTuple):
-    """`ASTER_V2.beam_decode`: device tensors, hypotheses in final (best first) order"""
+class _BeamFields(NamedTuple):
     symbols: torch.Tensor                   # int32 [B, k, L]
     scores: torch.Tensor                    # float32 [B, k] sum of log-probabilities; -inf = no such hypothesis
     lengths: torch.Tensor                   # int32 [B, k] t + 1 for a sequence that ended at step t, else L
     path_probs: Optional[torch.Tensor]      # float32 [B, L, C] rows of the best hypothesis, or None
+
+
+class BeamResult(_BeamFields):
+    """`ASTER_V2.beam_decode`: device tensors, hypotheses in final (best first) order.  The tuple keeps its four fields
+    (code that unpacks a result or rebuilds one from its fields is unaffected); `distributions` rides as an attribute:
+    float32 full per-step rows, [B, L, C] ("best") / [B, k, L, C] ("all"), default None."""
+
+    def __new__(cls, symbols, scores, lengths, path_probs=None, distributions=None):
+        self = super().__new__(cls, symbols, scores, lengths, path_probs)
+        self.distributions = distributions
+        return self
+
+
+class ForcedResult(NamedTuple):
+    """`ASTER_V2.score`: device tensors; the n axis is absent where the targets were given as [B, L]"""
+    step_logp: torch.Tensor                 # float32 [B, n, L] log-probability of targets[t] at step t; 0 from the length on
+    scores: torch.Tensor                    # float32 [B, n] float32 sum of step_logp[:length] in step order
+    lengths: torch.Tensor                   # int32 [B, n] steps computed
+    probs: Optional[torch.Tensor]           # float32 [B, n, L, C] softmax rows (zero from the length on), or None
+    logits: Optional[torch.Tensor]          # float32 [B, n, L, C] raw rows (zero from the length on), or None
 
 
 def build_recognizer_decoderv2(cfg, input_shape):
@@ -144,26 +168,101 @@ class ASTER_V2(InferenceModule):
         p = torch.cat(p, -1)[:, 0, :]
         return p.to(dev_), s[:, 0].to(dev_)
 
-    def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False) -> "BeamResult":
+    def _targets_to_device(self, targets, lengths, B: int, device):
+        """targets / lengths as `score` takes them -> (int32 [B,n,L] on `device`, int32 [B,n] | None, had_n_axis).  What comes
+        from the host (lists, numpy arrays, CPU tensors) is checked here, before anything is uploaded: shape, an integer
+        dtype, every symbol in [0, num_classes), every length in [0, L]; ValueError otherwise.  Device tensors are passed
+        through unread (the kernel checks the range itself and ends a sequence at a symbol outside it)."""
+        L, C = self.max_word_len, self.num_classes
+
+        def one(v, name, lo, hi, what):
+            on_device = torch.is_tensor(v) and v.device.type != "cpu"
+            t = v if torch.is_tensor(v) else torch.as_tensor(v)
+            if t.dtype.is_floating_point or t.dtype.is_complex or t.dtype == torch.bool:
+                raise ValueError(f"score: {name} must hold integers (got {t.dtype})")
+            if not on_device and t.numel() and (int(t.min()) < lo or int(t.max()) > hi):
+                raise ValueError(f"score: {name} outside {what} (found {int(t.min())}..{int(t.max())})")
+            return t, on_device
+        t, t_dev = one(targets, "targets", 0, C - 1, f"[0, {C})")
+        if t.dim() not in (2, 3) or t.shape[0] != B or t.shape[-1] != L:
+            raise ValueError(f"score: targets must be [B={B}, {L}] or [B={B}, n, {L}] (got {tuple(t.shape)})")
+        had_n = t.dim() == 3
+        t = t if had_n else t.unsqueeze(1)
+        if not 1 <= t.shape[1] <= 16:
+            raise ValueError(f"score: 1..16 sequences per item (got n={t.shape[1]})")
+        ln = None
+        if lengths is not None:
+            ln, l_dev = one(lengths, "lengths", 0, L, f"[0, {L}]")
+            ln = ln if had_n else ln.unsqueeze(-1)
+            if tuple(ln.shape) != tuple(t.shape[:2]):
+                raise ValueError(f"score: lengths {tuple(ln.shape)} do not match targets {tuple(t.shape)}")
+            ln = ln.to(torch.int32).contiguous() if l_dev else K.upload(ln.contiguous(), torch.int32, device)
+        t = t.to(torch.int32).contiguous() if t_dev else K.upload(t.contiguous(), torch.int32, device)
+        return t, ln, had_n
+
+    def score(self, x: torch.Tensor, targets, lengths=None, eos: int = 0, probs: bool = False, logits: bool = False) -> "ForcedResult":
+        """Forced decoding as ONE ABI call (glass_forced_decode): the decoder run with the emitted symbols GIVEN - "how likely
+        is this transcription under the model".  x [B,T,D]; targets [B,L] or [B,n,L] (L = max_word_len; n <= 16 sequences per
+        item share the item's x rows, which are not inflated): the symbol emitted at each step; lengths [B] / [B,n] or None
+        (None: each sequence runs up to and including its first `eos`).  -> ForcedResult on the device: per-step
+        log-probabilities of the given symbols, their float32 sum in step order, the lengths, and on request the full softmax
+        rows and raw logits per step; everything from a sequence's length on is zero."""
+        x = x.contiguous()
+        B, T, D = x.shape
+        t, ln, had_n = self._targets_to_device(targets, lengths, B, x.device)
+        xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x
+        out = K.forced_decode(x, xproj, self.w, t, ln, self.num_classes, self.max_word_len, int(eos), probs=probs, logits=logits)
+        if not had_n:
+            out = tuple(o.squeeze(1) if o is not None else None for o in out)
+        return ForcedResult(*out)
+
+    def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False,
+                    distributions: Optional[str] = None) -> "BeamResult":
         """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
         synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
         `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
         decoder's `pred_text_prob` read unchanged (arg-max = symbol, max = conditional probability of the step, zero rows
         from the hypothesis's length on).  Ties are ordered by flat candidate index, which `torch.topk` in `beam_search`
-        leaves open."""
+        leaves open.
+        `distributions`: "best" / "all" - after the search, ONE forced replay (glass_forced_decode) of hypothesis 0 / of all
+        k hypotheses with the search's lengths gives their FULL per-step softmax rows, [B,L,C] / [B,k,L,C]: what a consumer
+        that weighs every class of a step needs (the path rows hold one entry per step).  Rows from the length on, and every
+        row of a hypothesis whose score is -inf (its length is replaced by 0, on the device), are zero."""
+        if distributions not in (None, "best", "all"):
+            raise ValueError(f'beam_decode: distributions must be None, "best" or "all" (got {distributions!r})')
         x = x.contiguous()
         B, T, D = x.shape
         xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x      # empty batch: empty results
         out = K.beam_search(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos), path_probs=path_probs)
-        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None)
+        dist = None
+        if distributions is not None:
+            n = 1 if distributions == "best" else int(beam_width)
+            sym, sc, ln = out[0][:, :n].contiguous(), out[1][:, :n], out[2][:, :n]
+            ln = torch.where(torch.isneginf(sc), torch.zeros_like(ln), ln).contiguous()
+            dist = K.forced_decode(x, xproj, self.w, sym, ln, self.num_classes, self.max_word_len, int(eos), probs=True)[3]
+            dist = dist[:, 0] if distributions == "best" else dist
+        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist)
 
     def forward(self, features: torch.Tensor, labels=None, roi_image: Optional[torch.Tensor] = None,
                 num_images: int = 1, rnn=None, status=None) -> torch.Tensor:
         """features [R,T,D] -> probabilities [R,max_word_len,num_classes].  `roi_image` (int32 [R],
         image id per RoI) scopes the reference's early break to one image's RoIs; default: one call =
         one image, as in the reference.  `rnn` / `status`: as in BiLSTMBlockV2.forward_nhwc; without a `status` word
-        (the reference's call surface) the hand-off status is read here and a give-up re-runs the decoder on the step kernels."""
-        assert labels is None and not self.training, "inference only"
+        (the reference's call surface) the hand-off status is read here and a give-up re-runs the decoder on the step kernels.
+        With `labels` [R, max_word_len + 1] as TextEncoder.encode lays them out (slot 0 = [GO], the word from slot 1): the
+        reference's teacher-forced forward (AttentionRecognitionHead.forward, prediction_aster.py:33-60) - all max_word_len
+        steps, no stop, y_prev = labels[:, i] at step i - and the result is the LOGITS [R,max_word_len,num_classes]."""
+        assert not self.training, "inference only"
+        if labels is not None:
+            L = self.max_word_len
+            lab = labels if torch.is_tensor(labels) else torch.as_tensor(labels)
+            if lab.dim() != 2 or lab.shape[0] != features.shape[0] or lab.shape[1] != L + 1:
+                raise ValueError(f"forward: labels must be [R={features.shape[0]}, {L + 1}] (got {tuple(lab.shape)})")
+            # the reference's step i >= 1 reads y_prev = labels[:, i]: the symbol "emitted" at step t is labels[:, t + 1]
+            # (slot 0 is the [GO] the decoder starts from by itself; the last slot feeds no step)
+            targets = lab[:, 1:]
+            full = torch.full((lab.shape[0],), L, dtype=torch.int32)
+            return self.score(features, targets, full, eos=0, logits=True).logits
         if status is None and rnn != "steps":
             guard = K.HandoffGuard(features.device, owner=self)
             out = self.forward(features, labels, roi_image, num_images, rnn=getattr(self, "rnn_override", None) or rnn, status=guard.status)

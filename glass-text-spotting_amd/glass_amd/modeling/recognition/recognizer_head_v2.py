@@ -41,6 +41,12 @@ class RecognizerRCNNHeadV3(InferenceModule):
         # word score the consumers of `pred_text_prob` compute from the path rows is exp(score of the best hypothesis)
         ch = self.text_encoder.character
         self.beam_eos = ch.index("[s]") if "[s]" in ch else 0
+        # MI355X build only: with the search, also the best hypothesis's FULL per-step distributions (one forced replay,
+        # ASTER_V2.beam_decode(distributions="best")) as `pred_text_dist`, next to the path rows in `pred_text_prob`
+        self.beam_distributions = bool(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "BEAM_DISTRIBUTIONS", False))
+        if self.beam_distributions and self.beam_width < 1:
+            raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.BEAM_DISTRIBUTIONS needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 "
+                             f"(got BEAM_WIDTH {self.beam_width}): the greedy decoder's pred_text_prob already holds full rows")
 
     def import_weights(self, sd, device, prefix: str) -> None:
         self.backbone.import_weights(sd, device, prefix + "backbone.")
@@ -50,8 +56,9 @@ class RecognizerRCNNHeadV3(InferenceModule):
     rnn_override = None       # "steps" once K.HandoffGuard.STICKY_AFTER hand-off give-ups were seen by this head
     rnn_giveups = 0
 
-    def forward_nhwc(self, x: torch.Tensor, roi_image: torch.Tensor, num_images: int, guard=None) -> torch.Tensor:
-        """x [R,8,32,256] fused features -> probabilities [R,26,97] (BEAM_WIDTH >= 1: the best hypothesis's path rows).
+    def forward_nhwc(self, x: torch.Tensor, roi_image: torch.Tensor, num_images: int, guard=None):
+        """x [R,8,32,256] fused features -> probabilities [R,26,97] (BEAM_WIDTH >= 1: the best hypothesis's path rows; with
+        BEAM_DISTRIBUTIONS the pair (path rows, full distributions [R,26,97] of the best hypothesis) - `split_text_rows`).
         `guard` (ops.native.HandoffGuard): the one-launch BiLSTM / decoder kernels report a hand-off that gave up into
         `guard.status`, and `guard.retry` re-runs encoder + decoder of THIS call on the step kernels - the caller resolves the
         guard at its next host read-back (GeneralizedRCNN._postprocess_batched_g: the surviving-count read).  Without a guard
@@ -66,6 +73,9 @@ class RecognizerRCNNHeadV3(InferenceModule):
         def run(rnn, status):
             enc = self.encoder.forward_nhwc(f, rnn=rnn, status=status)
             if self.beam_width > 0:         # the search has no in-kernel hand-off: only the encoder is guarded
+                if self.beam_distributions:
+                    r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best")
+                    return r.path_probs, r.distributions
                 return self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True).path_probs
             return self.decoder(enc, roi_image=roi_image, num_images=num_images, rnn=rnn, status=status)
         if self.rnn_override == "steps":
@@ -85,10 +95,18 @@ class RecognizerRCNNHeadV3(InferenceModule):
         counts = [len(i) for i in instances]
         roi_image = K.upload(torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32), torch.tensor(counts)),
                              torch.int32, x.device)
-        preds = self.forward_nhwc(as_nhwc(x), roi_image, len(counts))
+        preds, dist = split_text_rows(self.forward_nhwc(as_nhwc(x), roi_image, len(counts)))
         for p, inst in zip(preds.split(counts, dim=0), instances):
             inst.pred_text_prob = p
+        if dist is not None:
+            for d, inst in zip(dist.split(counts, dim=0), instances):
+                inst.pred_text_dist = d
         return instances
+
+
+def split_text_rows(out):
+    """what `RecognizerRCNNHeadV3.forward_nhwc` returned -> (pred_text_prob rows, pred_text_dist rows | None)"""
+    return out if isinstance(out, tuple) else (out, None)
 
 
 def build_recognizer_head(cfg, input_shape):

@@ -1403,6 +1403,46 @@ def beam_search(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width:
     return (symbols, scores, lengths, path) if path_probs else (symbols, scores, lengths)
 
 
+def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: torch.Tensor, lengths: Optional[torch.Tensor],
+                  num_classes: int, max_len: int, eos: int, probs: bool = False, logits: bool = False):
+    """the decoder with the emitted symbols given (glass_forced_decode; reference AttentionRecognitionHead.forward): x, xproj
+    [B,T,D] un-inflated, targets int32 [B,n,max_len] and lengths int32 [B,n] (or None: up to and including the first `eos`)
+    on x's device -> (step_logp [B,n,max_len], scores [B,n], lengths int32 [B,n], probs [B,n,max_len,C] | None, logits
+    [B,n,max_len,C] | None).  No host synchronisation; limits are checked by the library."""
+    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj"); _i32(targets, "targets")
+    if xproj.shape != x.shape or xproj.device != x.device:
+        raise GlassLibraryError(f"forced_decode: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
+    B, T, D = x.shape
+    C, L = int(num_classes), int(max_len)
+    if targets.dim() != 3 or targets.shape[0] != B or targets.shape[2] != L or targets.device != x.device:
+        raise GlassLibraryError(f"forced_decode: targets {tuple(targets.shape)} on {targets.device} is not [B={B}, n, max_len={L}] on {x.device}")
+    n = int(targets.shape[1])
+    if lengths is not None:
+        _i32(lengths, "lengths")
+        if tuple(lengths.shape) != (B, n) or lengths.device != x.device:
+            raise GlassLibraryError(f"forced_decode: lengths {tuple(lengths.shape)} on {lengths.device} is not [B={B}, n={n}] on {x.device}")
+    dev = x.device
+    step_logp = torch.empty((B, n, max(L, 0)), dtype=torch.float32, device=dev)
+    scores = torch.empty((B, n), dtype=torch.float32, device=dev)
+    out_len = torch.empty((B, n), dtype=torch.int32, device=dev)
+    rows = (B, n, max(L, 0), max(C, 0))
+    out_probs = torch.empty(rows, dtype=torch.float32, device=dev) if probs else None
+    out_logits = torch.empty(rows, dtype=torch.float32, device=dev) if logits else None
+    w = DecoderWeights()
+    for name in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB"):
+        setattr(w, name, _dev(_f32c(weights[name], name)))
+    w.temperature = float(weights["temperature"])
+    nbytes = int(lib().glass_forced_decode_workspace_bytes(B, n, T, D, C, L))
+    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
+    check(lib().glass_forced_decode(c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), B, n, T, D, C, L, int(eos),
+                                    c_void_p(_dev(targets)), c_void_p(_dev(lengths)) if lengths is not None else None,
+                                    c_void_p(_dev(step_logp)), c_void_p(_dev(scores)), c_void_p(_dev(out_len)),
+                                    c_void_p(_dev(out_probs)) if out_probs is not None else None,
+                                    c_void_p(_dev(out_logits)) if out_logits is not None else None, c_void_p(_dev(ws)),
+                                    ctypes.c_int64(nbytes), c_void_p(stream_handle())), "glass_forced_decode")
+    return step_logp, scores, out_len, out_probs, out_logits
+
+
 def detections_finalize(boxes: torch.Tensor, scores: torch.Tensor, orient: Optional[torch.Tensor],
                         text: Optional[torch.Tensor], counts: torch.Tensor, roi_start: Optional[torch.Tensor],
                         scale_xy: torch.Tensor, out_hw: torch.Tensor, min_box_dim: float, do_filter_small: bool):

@@ -553,6 +553,27 @@ int glass_beam_search(const float* x, const float* xproj, const glass_decoder_we
                       int max_len, int eos, int* out_symbols, float* out_scores, int* out_lengths, float* out_path_probs,
                       void* workspace, int64_t workspace_bytes, glass_stream_t stream);
 
+/* FORCED decoding - the same decoder with the emitted symbols given, not chosen (AttentionRecognitionHead.forward,
+ * prediction_aster.py:33-60, teacher forcing): "how likely is this text under the model".  n sequences per item share the
+ * item's UN-inflated x / xproj rows [B,T,D] (a word to score, the k hypotheses of glass_beam_search, lexicon candidates).
+ *   targets [B,n,max_len] ints: the symbol emitted at each step; lengths [B,n] ints in 0..max_len (clamped), or null.
+ * Sequence j of item b: len = lengths[b,j] if given, else (position of the first `eos`) + 1, else max_len.  The state starts
+ * at zero; step t < len runs DecoderUnit.forward (:291-302) with y_prev = 0 ([GO]) at t = 0, else targets[t-1]:
+ *   out_step_logp[b,j,t] = lsm[targets[t]], lsm = fp32 log-softmax x - max - log(sum exp(x - max)) (glass_beam_search's);
+ *   score_t = fl32(score_{t-1} + step_logp[t]) added in step order from 0; out_scores[b,j] = score_{len-1}, 0 for len == 0;
+ *   out_lengths[b,j] = len;  out_probs[b,j,t,:] = exp(lsm) and out_logits[b,j,t,:] = the raw row (either may be null).
+ * Every entry at t >= len is zero (step_logp, probs, logits).  A symbol is never used as an index unchecked: a target
+ * outside [0,C) at t < len ends its sequence AT t (out_lengths = t, rows from t on zero) with out_scores = -inf.
+ * Needs D == 256, 1 <= T <= 64, 1 <= C <= 256, 1 <= n <= 16 (n may exceed C), 1 <= max_len <= 64; B == 0 returns GLASS_OK.
+ * `workspace` (16-byte aligned) >= glass_forced_decode_workspace_bytes().  2 * max_len + 1 launches (the GRU cell on the B*n
+ * state rows, one workgroup per item for the rest), no host synchronisation, bounded loops, no float atomics: results are
+ * bit-identical from run to run.  The logits are those of glass_attention_decode_step on inflated inputs.                  */
+int64_t glass_forced_decode_workspace_bytes(int B, int n, int T, int D, int C, int max_len);
+int glass_forced_decode(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T, int D, int C,
+                        int max_len, int eos, const int* targets, const int* lengths, float* out_step_logp, float* out_scores,
+                        int* out_lengths, float* out_probs, float* out_logits, void* workspace, int64_t workspace_bytes,
+                        glass_stream_t stream);
+
 /* ------------------------------------------------------------------ lexicon matching (evaluation)
  * find_match_word, un-weighted branch (glass/evaluation/lexicon_utils.py:4-28): for each query q, the word of lexicon segment
  * q_segment[q] at the smallest unit-cost Levenshtein distance, first strict minimum in file order.  Symbols are bytes, both
