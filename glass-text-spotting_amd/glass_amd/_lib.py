@@ -1,5 +1,9 @@
 """Loader / builder of libglass_hip.so (the C-ABI kernel library, include/glass_hip.h).
 
+The header is the one description of the ABI: `signatures()` parses its prototypes, `EXPORTS` is their names, and `lib()`
+gives every entry its `restype` / `argtypes` from them - ctypes then converts plain ints, floats and `None`, passes 64-bit
+sizes and device addresses whole, and refuses a wrongly typed argument on the host (`ctypes.ArgumentError`).
+
 The product path has NO CPU fallback: `lib()` raises if the shared object is missing or
 does not export every declared symbol, and every op wrapper raises if its tensors are not
 on a HIP device.
@@ -9,8 +13,9 @@ from __future__ import annotations
 import ctypes
 import glob
 import os
+import re
 import subprocess
-from typing import List, Optional
+from typing import Dict, List, Optional, Tuple
 
 _PKG = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_PKG)                     # glass-text-spotting_amd/
@@ -18,34 +23,53 @@ CSRC = os.path.join(_ROOT, "csrc")
 INCLUDE = os.path.join(os.path.dirname(_ROOT), "include")
 SO_PATH = os.environ.get("GLASS_HIP_LIB") or os.path.join(_ROOT, "libglass_hip.so")   # override: kernel experiments
 
-EXPORTS = [
-    "glass_last_error", "glass_abi_version", "glass_device_count", "glass_conv2d_nhwc", "glass_conv2d_nhwc_f16", "glass_conv2d_nhwc_h16", "glass_local_stem_supported", "glass_local_stem_fused", "glass_local_stem_fused_h16", "glass_backbone_stem_supported", "glass_backbone_stem_fused", "glass_conv3x3_winograd43_body_nhwc", "glass_winograd43_splitk_supported", "glass_winograd43_splitk_workspace_bytes", "glass_conv3x3_winograd43_splitk_nhwc", "glass_roi_align_rotated_up2", "glass_conv2d_splitk_supported", "glass_conv2d_splitk_workspace_bytes", "glass_conv2d_nhwc_splitk", "glass_conv3x3_winograd_body_nhwc",
-    "glass_pointwise_supported", "glass_pointwise_weight_floats", "glass_pointwise_pack_weights", "glass_conv1x1_pointwise_nhwc",
-    "glass_pointwise_split_supported", "glass_pointwise_split_weight_bytes", "glass_pointwise_split_pack_weights", "glass_conv1x1_pointwise_split_nhwc", "glass_pointwise_split_dual_supported", "glass_conv1x1_pointwise_split_dual_nhwc",
-    "glass_conv_h16_supported", "glass_conv_h16_weight_halves", "glass_conv_h16_pack_weights", "glass_conv2d_nhwc_h16_packed",
-    "glass_winograd_supported", "glass_winograd_block_channels", "glass_winograd_weight_floats", "glass_winograd_pack_weights", "glass_conv3x3_winograd_nhwc",
-    "glass_winograd43_supported", "glass_winograd43_weight_floats", "glass_winograd43_pack_weights", "glass_conv3x3_winograd43_nhwc",
-    "glass_winograd43_ragged_supported", "glass_conv3x3_winograd43_ragged_nhwc",
-    "glass_maxpool2d_nhwc", "glass_maxpool2d_nhwc_h16", "glass_roi_align_rotated_h16", "glass_pixel_shuffle2x_nhwc", "glass_sigmoid_inplace", "glass_paste_rotated_masks", "glass_mul_inplace", "glass_cast_f32_to_f16",
-    "glass_preprocess_image", "glass_image_u8hwc_to_chw_resized", "glass_roi_align_rotated",
-    "glass_rpn_workspace_bytes", "glass_rpn_topk_decode", "glass_rotated_nms_select", "glass_pairwise_iou_rotated", "glass_detections_finalize", "glass_postprocess_words", "glass_postprocess_words_dense_workspace_bytes", "glass_postprocess_words_dense", "glass_text_argmax", "glass_pack_word_records",
-    "glass_box_decode", "glass_gc_attention_inplace", "glass_mean_over_h", "glass_bilstm_workspace_bytes", "glass_bilstm_recurrence",
-    "glass_bilstm_persistent_workspace_bytes", "glass_bilstm_recurrence_persistent", "glass_recurrence_status", "glass_recurrence_test_hook",
-    "glass_decode_persistent_supported", "glass_decode_persistent_workspace_bytes", "glass_attention_decode_persistent",
-    "glass_decode_workspace_bytes", "glass_attention_decode", "glass_decode_step_workspace_bytes", "glass_attention_decode_step",
-    "glass_beam_search_workspace_bytes", "glass_beam_search", "glass_forced_decode_workspace_bytes", "glass_forced_decode",
-    "glass_lexicon_match_workspace_bytes", "glass_lexicon_match",
-    "glass_lexicon_match_weighted_workspace_bytes", "glass_lexicon_match_weighted",
-    "glass_rrc_pair_areas_workspace_bytes", "glass_rrc_pair_areas", "glass_rrc_match_workspace_bytes", "glass_rrc_match",
-    "glass_rrc_sweep_workspace_bytes", "glass_rrc_sweep",
-    "glass_mask_windows", "glass_mask_rings_workspace_bytes", "glass_mask_rings_count", "glass_mask_rings_write",
-    "glass_ring_check_tasks", "glass_ring_check",
-    "glass_resize_pil_workspace_bytes", "glass_resize_u8_pil", "glass_resize_u8_pil_into_batch",
-]
-
 
 class GlassLibraryError(RuntimeError):
     pass
+
+
+_RESTYPES = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t, "const char*": ctypes.c_char_p}
+_ARGTYPES = {"glass_stream_t": ctypes.c_void_p, "int": ctypes.c_int, "int64_t": ctypes.c_int64, "size_t": ctypes.c_size_t,
+             "float": ctypes.c_float, "double": ctypes.c_double}
+_SIGNATURES: Optional[Dict[str, Tuple[object, list]]] = None
+
+
+def signatures(header: Optional[str] = None) -> Dict[str, Tuple[object, list]]:
+    """{name: (restype, [argtypes])} of every glass_* prototype of include/glass_hip.h (parsed once), or of the header text
+    given.  A prototype starts in column 0 with its return type and may span lines; any parameter with a `*` and
+    glass_stream_t are c_void_p (which also takes `ctypes.byref(desc)` and ctypes arrays).  Nothing has a default: a return
+    or parameter type not listed above (a struct by value, a new typedef) raises, and so does a `glass_*(` name for which
+    no prototype was parsed."""
+    global _SIGNATURES
+    if header is None:
+        if _SIGNATURES is None:
+            with open(os.path.join(INCLUDE, "glass_hip.h")) as fh:
+                _SIGNATURES = signatures(fh.read())
+        return _SIGNATURES
+    text = re.sub(r"/\*.*?\*/", "", header, flags=re.S)
+    sigs = {}
+    for ret, name, params in re.findall(r"^(\w[\w \t*]*?)\s*\b(glass_\w+)\s*\(([^()]*)\)\s*;", text, flags=re.M):
+        ret = re.sub(r"\s*\*", "*", " ".join(ret.split()))
+        if ret not in _RESTYPES:
+            raise GlassLibraryError(f"include/glass_hip.h: {name} returns {ret!r}, which the binding does not know")
+        argtypes = []
+        for prm in ([] if params.strip() == "void" else params.split(",")):
+            words = [t for t in prm.split() if t != "const"]
+            if "*" in prm:
+                argtypes.append(ctypes.c_void_p)
+            elif len(words) == 2 and words[0] in _ARGTYPES and "[" not in prm:
+                argtypes.append(_ARGTYPES[words[0]])
+            else:
+                raise GlassLibraryError(f"include/glass_hip.h: {name} has parameter {' '.join(prm.split())!r}, "
+                                        "which the binding does not know")
+        sigs[name] = (_RESTYPES[ret], argtypes)
+    unparsed = sorted(set(re.findall(r"\b(glass_\w+)\s*\(", text)) - set(sigs))
+    if unparsed:
+        raise GlassLibraryError(f"include/glass_hip.h: no prototype parsed for {unparsed}")
+    return sigs
+
+
+EXPORTS = list(signatures())        # every entry point the header declares, in its order
 
 
 # Device code is compiled WITHOUT packed-f32 (v_pk_*_f32) and fma_mix instruction selection.  On MI355X / ROCm 7.2 a VOP3P
@@ -124,40 +148,9 @@ def lib() -> ctypes.CDLL:
         missing = [s for s in EXPORTS if not hasattr(L, s)]
         if missing:
             raise GlassLibraryError(f"{SO_PATH} lacks symbols {missing}")
-        L.glass_last_error.restype = ctypes.c_char_p
-        L.glass_rpn_workspace_bytes.restype = ctypes.c_int64
-        L.glass_winograd_weight_floats.restype = ctypes.c_size_t
-        L.glass_winograd43_weight_floats.restype = ctypes.c_size_t
-        L.glass_pointwise_weight_floats.restype = ctypes.c_size_t
-        L.glass_pointwise_split_weight_bytes.restype = ctypes.c_size_t
-        L.glass_conv_h16_weight_halves.restype = ctypes.c_size_t
-        L.glass_bilstm_workspace_bytes.restype = ctypes.c_int64
-        L.glass_bilstm_persistent_workspace_bytes.restype = ctypes.c_int64
-        L.glass_decode_persistent_workspace_bytes.restype = ctypes.c_int64
-        L.glass_decode_workspace_bytes.restype = ctypes.c_int64
-        L.glass_decode_step_workspace_bytes.restype = ctypes.c_int64
-        L.glass_beam_search_workspace_bytes.restype = ctypes.c_int64
-        L.glass_forced_decode_workspace_bytes.restype = ctypes.c_int64
-        L.glass_conv2d_splitk_workspace_bytes.restype = ctypes.c_int64
-        L.glass_winograd43_splitk_workspace_bytes.restype = ctypes.c_int64
-        L.glass_lexicon_match_workspace_bytes.restype = ctypes.c_int64
-        L.glass_lexicon_match_weighted_workspace_bytes.restype = ctypes.c_int64
-        L.glass_lexicon_match_weighted_workspace_bytes.argtypes = [ctypes.c_int, ctypes.c_int]
-        _p, _i, _l = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-        L.glass_lexicon_match_weighted.restype = ctypes.c_int
-        L.glass_lexicon_match_weighted.argtypes = [_p, _p, _p, _i, _p, _l, _p, _p, _i, _i, _p, _p, _p, _p, _i, _p, _i, _i,
-                                                   _p, _p, _p, _p, _l, _p]
-        L.glass_rrc_pair_areas_workspace_bytes.restype = ctypes.c_int64
-        L.glass_rrc_match_workspace_bytes.restype = ctypes.c_int64
-        L.glass_rrc_sweep_workspace_bytes.restype = ctypes.c_int64
-        L.glass_postprocess_words_dense_workspace_bytes.restype = ctypes.c_int64
-        L.glass_mask_rings_workspace_bytes.restype = ctypes.c_int64
-        L.glass_ring_check_tasks.restype = ctypes.c_int64
-        L.glass_resize_pil_workspace_bytes.restype = ctypes.c_int64
-        L.glass_resize_u8_pil.restype = ctypes.c_int
-        L.glass_resize_u8_pil.argtypes = [_p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _l, _p, _i, _i, _p]
-        L.glass_resize_u8_pil_into_batch.restype = ctypes.c_int
-        L.glass_resize_u8_pil_into_batch.argtypes = [_p, _i, _i, _p, _p, _i, _p, _p, _i, _p, _l, _i, _i, _p, _p, _i, _p, _i, _i, _i, _p]
+        for name, (restype, argtypes) in signatures().items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = restype, argtypes
         _LIB = L
     return _LIB
 

@@ -2,6 +2,11 @@
 
 torch is used only for device memory and the current HIP stream.  Every wrapper refuses
 CPU tensors: there is no fallback path.
+
+`_lib.lib()` has given every entry point the `argtypes` of its prototype in the header, so a call passes plain values:
+`_dev(t)` / `_opt(t)` addresses (or None) for pointers, `ctypes.byref(desc)` for the descriptor structs, ctypes arrays for
+the small host tables, ints and floats as they are - ctypes widens them to the declared type and raises
+`ctypes.ArgumentError` for a value of the wrong kind.  No call site wraps an argument in a ctypes type.
 """
 from __future__ import annotations
 
@@ -33,9 +38,11 @@ class RoiAlignDesc(ctypes.Structure):
                 ("sampling_ratio", c_int), ("ldy", c_int), ("y_coff", c_int), ("y_cstride", c_int)]
 
 
+_DECODER_TENSORS = ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB")
+
+
 class DecoderWeights(ctypes.Structure):
-    _fields_ = [(n, c_void_p) for n in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB")] + \
-               [("temperature", c_float)]
+    _fields_ = [(n, c_void_p) for n in _DECODER_TENSORS] + [("temperature", c_float)]
 
 
 def _dev(t: torch.Tensor, name: str = "tensor") -> int:
@@ -43,6 +50,17 @@ def _dev(t: torch.Tensor, name: str = "tensor") -> int:
         raise GlassLibraryError(f"{name} must live on a HIP device (got {getattr(t, 'device', type(t))}); "
                                 "the GLASS hot path has no CPU fallback")
     return t.data_ptr()
+
+
+def _opt(t: Optional[torch.Tensor], name: str = "tensor") -> Optional[int]:
+    """an optional operand: None (a null pointer for the library) or the checked device address"""
+    return None if t is None else _dev(t, name)
+
+
+def _workspace(nbytes: int, device) -> torch.Tensor:
+    """scratch of the *_workspace_bytes() a launch asked for (never empty, so never a null pointer; the caching allocator
+    hands out 512-byte multiples anyway); stream-ordered reuse after the wrapper returns is the allocator's business"""
+    return torch.empty((max(int(nbytes), 16),), dtype=torch.uint8, device=device)
 
 
 def _f32c(t: torch.Tensor, name: str) -> torch.Tensor:
@@ -300,12 +318,12 @@ def winograd_pack(w: torch.Tensor, f43=False) -> torch.Tensor:
         return w[:, :, 0:2, :].reshape(Cout, 3, 1, 2 * Cin).contiguous()
     if f43 == "h16":
         u = torch.empty((int(L.glass_conv_h16_weight_halves(Cout, KH, KW, Cin)),), dtype=torch.float16, device=w.device)
-        check(L.glass_conv_h16_pack_weights(c_void_p(_dev(w, "w")), Cout, KH, KW, Cin, c_void_p(_dev(u)), c_void_p(stream_handle())),
+        check(L.glass_conv_h16_pack_weights(_dev(w, "w"), Cout, KH, KW, Cin, _dev(u), stream_handle()),
               "glass_conv_h16_pack_weights")
         return u
     if f43 == "pws":
         u = torch.empty((int(L.glass_pointwise_split_weight_bytes(Cout, Cin)),), dtype=torch.uint8, device=w.device)
-        check(L.glass_pointwise_split_pack_weights(c_void_p(_dev(w, "w")), Cout, Cin, c_void_p(_dev(u)), c_void_p(stream_handle())),
+        check(L.glass_pointwise_split_pack_weights(_dev(w, "w"), Cout, Cin, _dev(u), stream_handle()),
               "glass_pointwise_split_pack_weights")
         return u
     if f43 == "pw":
@@ -315,7 +333,7 @@ def winograd_pack(w: torch.Tensor, f43=False) -> torch.Tensor:
     else:
         nf, fn, what = L.glass_winograd_weight_floats, L.glass_winograd_pack_weights, "glass_winograd_pack_weights"
     u = torch.empty((int(nf(Cout, Cin)),), dtype=torch.float32, device=w.device)
-    check(fn(c_void_p(_dev(w, "w")), Cout, Cin, c_void_p(_dev(u)), c_void_p(stream_handle())), what)
+    check(fn(_dev(w, "w"), Cout, Cin, _dev(u), stream_handle()), what)
     return u
 
 
@@ -727,18 +745,16 @@ def conv2d_nhwc(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, *, stri
     xt = x
     if cast:
         xt = torch.empty(x.shape, dtype=torch.float16, device=x.device)
-        check(L.glass_cast_f32_to_f16(c_void_p(_dev(x, "x")), c_void_p(_dev(xt)), ctypes.c_int64(x.numel()),
-                                      c_void_p(stream_handle())), "glass_cast_f32_to_f16")
+        check(L.glass_cast_f32_to_f16(_dev(x, "x"), _dev(xt), x.numel(), stream_handle()), "glass_cast_f32_to_f16")
     # every conv entry: (desc, x, w | packed weights, bias, residual, y[, splits][, flags][, workspace, bytes], stream)
-    args = [ctypes.byref(d), c_void_p(_dev(xt, "x")), c_void_p(_dev(wt if pack is None else _packed(w, wt, pack), "w")),
-            c_void_p(_dev(bias, "bias") if bias is not None else None),
-            c_void_p(_dev(residual, "residual") if residual is not None else None), c_void_p(_dev(out, "out"))]
+    args = [ctypes.byref(d), _dev(xt, "x"), _dev(wt if pack is None else _packed(w, wt, pack), "w"), _opt(bias, "bias"),
+            _opt(residual, "residual"), _dev(out, "out")]
     tail = [] if flags is None else [flags]
     if splits:
         nbytes = int(getattr(L, _WORKSPACE_BYTES[entry])(ctypes.byref(d), splits))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        tail = [splits] + tail + [c_void_p(_dev(ws)), ctypes.c_int64(nbytes)]
-    check(getattr(L, entry)(*args, *tail, c_void_p(stream_handle())), entry)
+        ws = _workspace(nbytes, x.device)
+        tail = [splits] + tail + [_dev(ws), nbytes]
+    check(getattr(L, entry)(*args, *tail, stream_handle()), entry)
     if strip:
         _last_column_strip(x, _packed(w, wt, "col1"), bias, residual, out, d, out_coff)
     return out
@@ -794,10 +810,10 @@ def conv1x1_dual_nhwc(x1: torch.Tensor, x2: torch.Tensor, w: "ConvWeight", bias:
     out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x1.device)
     d = ConvDesc(N, H, W, Cin1, Cout, 1, 1, stride, stride, 0, 0, Ho, Wo, ldx, Cout, 0, 1, relu, 0, 0)
     _TLS.last_path = "pointwise_split"
-    check(lib().glass_conv1x1_pointwise_split_dual_nhwc(
-        ctypes.byref(d), c_void_p(_dev(x1, "x1")), c_void_p(_dev(x2, "x2")), int(Cin2), int(x2.shape[3]), c_void_p(_dev(_packed(w, w.raw, "pws"), "w")),
-        c_void_p(_dev(bias, "bias") if bias is not None else None), c_void_p(_dev(out, "out")), c_void_p(stream_handle())),
-        "glass_conv1x1_pointwise_split_dual_nhwc")
+    check(lib().glass_conv1x1_pointwise_split_dual_nhwc(ctypes.byref(d), _dev(x1, "x1"), _dev(x2, "x2"), int(Cin2),
+                                                        int(x2.shape[3]), _dev(_packed(w, w.raw, "pws"), "w"), _opt(bias, "bias"),
+                                                        _dev(out, "out"), stream_handle()),
+          "glass_conv1x1_pointwise_split_dual_nhwc")
     return out
 
 
@@ -812,9 +828,8 @@ def _last_column_strip(x: torch.Tensor, wcol: torch.Tensor, bias, residual, out:
     isz = x.element_size()
     xp = _dev(x, "x") + (W - 2) * d.ldx * isz
     rp = (_dev(residual, "residual") + (W - 1) * d.ldr * residual.element_size()) if (residual is not None and d.res_mode) else None
-    check(lib().glass_conv2d_nhwc(ctypes.byref(ds), c_void_p(xp), c_void_p(_dev(wcol, "w")),
-                                  c_void_p(_dev(bias, "bias") if bias is not None else None), c_void_p(rp), c_void_p(_dev(out, "out")),
-                                  c_void_p(stream_handle())), "glass_conv2d_nhwc(last column)")
+    check(lib().glass_conv2d_nhwc(ctypes.byref(ds), xp, _dev(wcol, "w"), _opt(bias, "bias"), rp, _dev(out, "out"), stream_handle()),
+          "glass_conv2d_nhwc(last column)")
 
 
 def _splitk_slices(rt: Routing, M: int, Ktot: int, Cin: int, Cout: int, want_time: bool = False):
@@ -881,8 +896,7 @@ def local_stem_fused(x: torch.Tensor, w1, b1: torch.Tensor, w2, b2: torch.Tensor
     R, H, W, _ = x.shape
     y = torch.empty((R, H // 2, W // 2, 32), dtype=torch.float16 if h16 else torch.float32, device=x.device)
     fn = lib().glass_local_stem_fused_h16 if h16 else lib().glass_local_stem_fused
-    check(fn(c_void_p(_dev(x)), c_void_p(_dev(w1)), c_void_p(_dev(b1)), c_void_p(_dev(w2)), c_void_p(_dev(b2)), c_void_p(_dev(y)),
-             R, H, W, c_void_p(stream_handle())), "glass_local_stem_fused")
+    check(fn(_dev(x), _dev(w1), _dev(b1), _dev(w2), _dev(b2), _dev(y), R, H, W, stream_handle()), "glass_local_stem_fused")
     return y
 
 
@@ -902,8 +916,8 @@ def backbone_stem_fused(x: torch.Tensor, w, bias: torch.Tensor) -> torch.Tensor:
         _f32c(t, n)
     N, H, W, _ = x.shape
     y = torch.empty((N, H // 4, W // 4, 64), dtype=torch.float32, device=x.device)
-    check(lib().glass_backbone_stem_fused(c_void_p(_dev(x)), c_void_p(_dev(wt)), c_void_p(_dev(bias)), c_void_p(_dev(y)), N, H, W,
-                                          c_void_p(stream_handle())), "glass_backbone_stem_fused")
+    check(lib().glass_backbone_stem_fused(_dev(x), _dev(wt), _dev(bias), _dev(y), N, H, W, stream_handle()),
+          "glass_backbone_stem_fused")
     _TLS.last_path = "fused_stem"
     return y
 
@@ -917,8 +931,7 @@ def maxpool2d_nhwc(x: torch.Tensor, kernel, stride, padding=0) -> torch.Tensor:
     Ho, Wo = (H + 2 * ph - KH) // sh + 1, (W + 2 * pw - KW) // sw + 1
     y = torch.empty((N, Ho, Wo, C), dtype=x.dtype, device=x.device)
     fn = lib().glass_maxpool2d_nhwc_h16 if x.dtype == torch.float16 else lib().glass_maxpool2d_nhwc
-    check(fn(c_void_p(_dev(x)), c_void_p(_dev(y)), N, H, W, C, KH, KW, sh, sw, ph, pw, Ho, Wo, c_void_p(stream_handle())),
-          "glass_maxpool2d_nhwc")
+    check(fn(_dev(x), _dev(y), N, H, W, C, KH, KW, sh, sw, ph, pw, Ho, Wo, stream_handle()), "glass_maxpool2d_nhwc")
     return y
 
 
@@ -928,8 +941,7 @@ def pixel_shuffle2x_nhwc(x: torch.Tensor) -> torch.Tensor:
     N, H, W, C4 = x.shape
     C = C4 // 4
     y = torch.empty((N, 2 * H, 2 * W, C), dtype=torch.float32, device=x.device)
-    check(lib().glass_pixel_shuffle2x_nhwc(c_void_p(_dev(x)), c_void_p(_dev(y)), N, H, W, C, c_void_p(stream_handle())),
-          "glass_pixel_shuffle2x_nhwc")
+    check(lib().glass_pixel_shuffle2x_nhwc(_dev(x), _dev(y), N, H, W, C, stream_handle()), "glass_pixel_shuffle2x_nhwc")
     return y
 
 
@@ -937,15 +949,13 @@ def mul_(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     _f32c(a, "a"); _f32c(b, "b")
     if a.shape != b.shape:
         raise GlassLibraryError(f"mul_: shapes {tuple(a.shape)} vs {tuple(b.shape)}")
-    check(lib().glass_mul_inplace(c_void_p(_dev(a)), c_void_p(_dev(b)), ctypes.c_int64(a.numel()), c_void_p(stream_handle())),
-          "glass_mul_inplace")
+    check(lib().glass_mul_inplace(_dev(a), _dev(b), a.numel(), stream_handle()), "glass_mul_inplace")
     return a
 
 
 def sigmoid_(x: torch.Tensor) -> torch.Tensor:
     _f32c(x, "x")
-    check(lib().glass_sigmoid_inplace(c_void_p(_dev(x)), ctypes.c_int64(x.numel()), c_void_p(stream_handle())),
-          "glass_sigmoid_inplace")
+    check(lib().glass_sigmoid_inplace(_dev(x), x.numel(), stream_handle()), "glass_sigmoid_inplace")
     return x
 
 
@@ -958,8 +968,8 @@ def paste_rotated_masks(masks: torch.Tensor, boxes: torch.Tensor, image_hw: Tupl
     H, W = int(image_hw[0]), int(image_hw[1])
     out = torch.empty((R, H, W), dtype=torch.uint8, device=masks.device)
     if R:
-        check(lib().glass_paste_rotated_masks(c_void_p(_dev(masks)), c_void_p(_dev(boxes)), R, M, H, W, c_float(threshold),
-                                              c_void_p(_dev(out)), c_void_p(stream_handle())), "glass_paste_rotated_masks")
+        check(lib().glass_paste_rotated_masks(_dev(masks), _dev(boxes), R, M, H, W, threshold, _dev(out), stream_handle()),
+              "glass_paste_rotated_masks")
     return out.view(torch.bool) if threshold >= 0 else out
 
 
@@ -971,8 +981,8 @@ def preprocess_image(chw: torch.Tensor, mean: Sequence[float], std: Sequence[flo
     assert four == 4
     m = (c_float * 3)(*[float(v) for v in mean])
     s = (c_float * 3)(*[float(v) for v in std])
-    check(lib().glass_preprocess_image(c_void_p(_dev(chw)), H, W, m, s, c_void_p(_dev(batch)), int(n), Hp, Wp,
-                                       c_void_p(stream_handle())), "glass_preprocess_image")
+    check(lib().glass_preprocess_image(_dev(chw), H, W, m, s, _dev(batch), int(n), Hp, Wp, stream_handle()),
+          "glass_preprocess_image")
 
 
 def image_u8hwc_to_chw(img: torch.Tensor, out_hw: Tuple[int, int], flip_channels: bool = False) -> torch.Tensor:
@@ -981,9 +991,8 @@ def image_u8hwc_to_chw(img: torch.Tensor, out_hw: Tuple[int, int], flip_channels
     H, W, C = img.shape
     assert C == 3
     out = torch.empty((3, out_hw[0], out_hw[1]), dtype=torch.float32, device=img.device)
-    check(lib().glass_image_u8hwc_to_chw_resized(c_void_p(_dev(img)), H, W, c_void_p(_dev(out)), out_hw[0], out_hw[1],
-                                                 int(flip_channels), c_void_p(stream_handle())),
-          "glass_image_u8hwc_to_chw_resized")
+    check(lib().glass_image_u8hwc_to_chw_resized(_dev(img), H, W, _dev(out), int(out_hw[0]), int(out_hw[1]), int(flip_channels),
+                                                 stream_handle()), "glass_image_u8hwc_to_chw_resized")
     return out
 
 
@@ -1016,7 +1025,7 @@ def _pil_resize_args(img: torch.Tensor, out_hw: Tuple[int, int]):
     Ho, Wo = int(out_hw[0]), int(out_hw[1])
     kx, bx, nx = _pil_tables(W, Wo, img.device)
     ky, by, ny = _pil_tables(H, Ho, img.device)
-    ptr = lambda t: c_void_p(t.data_ptr() if t is not None else None)       # noqa: E731
+    ptr = lambda t: t.data_ptr() if t is not None else None       # noqa: E731
     return H, W, Ho, Wo, (ptr(kx), ptr(bx), nx, ptr(ky), ptr(by), ny), (kx, bx, ky, by)
 
 
@@ -1032,9 +1041,8 @@ def pil_resize_u8(img: torch.Tensor, out_hw: Tuple[int, int], workspace: Optiona
     H, W, Ho, Wo, tables, _keep = _pil_resize_args(img, out_hw)
     out = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=img.device)
     ws = workspace if workspace is not None else pil_resize_workspace(H, W, Ho, Wo, img.device)
-    check(lib().glass_resize_u8_pil(c_void_p(_dev(img)), H, W, *tables, c_void_p(_dev(ws) if ws is not None else None),
-                                    ws.numel() * ws.element_size() if ws is not None else 0, c_void_p(_dev(out)), Ho, Wo,
-                                    c_void_p(stream_handle())), "glass_resize_u8_pil")
+    check(lib().glass_resize_u8_pil(_dev(img), H, W, *tables, _opt(ws), ws.numel() * ws.element_size() if ws is not None else 0,
+                                    _dev(out), Ho, Wo, stream_handle()), "glass_resize_u8_pil")
     return out
 
 
@@ -1053,9 +1061,9 @@ def pil_resize_into_batch(img: torch.Tensor, out_hw: Tuple[int, int], mean: Sequ
     m = (c_float * 3)(*[float(v) for v in mean])
     s = (c_float * 3)(*[float(v) for v in std])
     ws = workspace if workspace is not None else pil_resize_workspace(H, W, Ho, Wo, img.device)
-    check(lib().glass_resize_u8_pil_into_batch(c_void_p(_dev(img)), H, W, *tables, c_void_p(_dev(ws) if ws is not None else None),
-                                               ws.numel() * ws.element_size() if ws is not None else 0, Ho, Wo, m, s, int(flip_channels),
-                                               c_void_p(_dev(batch)), int(n), Hp, Wp, c_void_p(stream_handle())),
+    check(lib().glass_resize_u8_pil_into_batch(_dev(img), H, W, *tables, _opt(ws),
+                                               ws.numel() * ws.element_size() if ws is not None else 0, Ho, Wo, m, s,
+                                               int(flip_channels), _dev(batch), int(n), Hp, Wp, stream_handle()),
           "glass_resize_u8_pil_into_batch")
 
 
@@ -1089,8 +1097,8 @@ def roi_align_rotated(feats: List[torch.Tensor], scales: Sequence[float], boxes:
         if up2 and half:
             raise GlassLibraryError("roi_align_rotated(up2=True) takes fp32 levels")
         fn = lib().glass_roi_align_rotated_up2 if up2 else (lib().glass_roi_align_rotated_h16 if half else lib().glass_roi_align_rotated)
-        check(fn(ctypes.byref(d), c_void_p(_dev(boxes)), c_void_p(_dev(batch_idx)), R, c_void_p(_dev(_f32c(out, "out"))),
-                 c_void_p(stream_handle())), "glass_roi_align_rotated")
+        check(fn(ctypes.byref(d), _dev(boxes), _dev(batch_idx), R, _dev(_f32c(out, "out")), stream_handle()),
+              "glass_roi_align_rotated")
     return out
 
 
@@ -1118,12 +1126,10 @@ def rpn_topk_decode(levels: Sequence[dict], N: int, A: int, anchor_offset: float
         for k in ("ldl", "ldd", "H", "W", "stride", "topk", "slot_off"):
             setattr(arr[i], k, int(lv[k]))
     nbytes = int(lib().glass_rpn_workspace_bytes(N, L))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=out_boxes.device)
+    ws = _workspace(nbytes, out_boxes.device)
     w = (c_float * 5)(*[float(v) for v in weights])
-    check(lib().glass_rpn_topk_decode(arr, L, N, A, c_float(anchor_offset), w, int(out_boxes.shape[1]),
-                                      c_void_p(_dev(out_boxes)), c_void_p(_dev(out_scores)), c_void_p(_dev(out_level)),
-                                      c_void_p(_dev(ws)), ctypes.c_int64(nbytes), c_void_p(stream_handle())),
-          "glass_rpn_topk_decode")
+    check(lib().glass_rpn_topk_decode(arr, L, N, A, anchor_offset, w, int(out_boxes.shape[1]), _dev(out_boxes), _dev(out_scores),
+                                      _dev(out_level), _dev(ws), nbytes, stream_handle()), "glass_rpn_topk_decode")
 
 
 NMS_CLIP, NMS_DROP_EMPTY = 1, 2
@@ -1151,12 +1157,10 @@ def rotated_nms_select(boxes: torch.Tensor, scores: torch.Tensor, cat: Optional[
     dev = boxes.device
     ob, os_, oi, oc = zeros_views([((N, post_topk, 5), torch.float32), ((N, post_topk), torch.float32), ((N, post_topk), torch.int32),
                                    ((N,), torch.int32)], dev)
-    check(lib().glass_rotated_nms_select(
-        c_void_p(_dev(boxes)), c_void_p(_dev(scores)), c_void_p(_dev(_i32(cat, "cat")) if cat is not None else None),
-        c_void_p(_dev(_i32(valid_count, "valid_count")) if valid_count is not None else None), N, S,
-        c_void_p(_dev(image_hw)), c_float(score_thresh), c_float(nms_thresh), int(post_topk), int(flags),
-        c_void_p(_dev(ob)), c_void_p(_dev(os_)), c_void_p(_dev(oi)), c_void_p(_dev(oc)), c_void_p(stream_handle())),
-        "glass_rotated_nms_select")
+    check(lib().glass_rotated_nms_select(_dev(boxes), _dev(scores), _opt(None if cat is None else _i32(cat, "cat")),
+                                         _opt(None if valid_count is None else _i32(valid_count, "valid_count")), N, S,
+                                         _dev(image_hw), score_thresh, nms_thresh, int(post_topk), int(flags), _dev(ob), _dev(os_),
+                                         _dev(oi), _dev(oc), stream_handle()), "glass_rotated_nms_select")
     return ob, os_, oi, oc
 
 
@@ -1164,8 +1168,8 @@ def pairwise_iou_rotated(b1: torch.Tensor, b2: torch.Tensor) -> torch.Tensor:
     _f32c(b1, "boxes1"); _f32c(b2, "boxes2")
     out = torch.zeros((b1.shape[0], b2.shape[0]), dtype=torch.float32, device=b1.device)
     if out.numel():
-        check(lib().glass_pairwise_iou_rotated(c_void_p(_dev(b1)), b1.shape[0], c_void_p(_dev(b2)), b2.shape[0],
-                                               c_void_p(_dev(out)), c_void_p(stream_handle())), "glass_pairwise_iou_rotated")
+        check(lib().glass_pairwise_iou_rotated(_dev(b1), b1.shape[0], _dev(b2), b2.shape[0], _dev(out), stream_handle()),
+              "glass_pairwise_iou_rotated")
     return out
 
 
@@ -1180,9 +1184,8 @@ def box_decode(cls_logits: torch.Tensor, deltas: torch.Tensor, orient_logits: to
     if R:
         for t, nm in ((cls_logits, "cls"), (deltas, "deltas"), (orient_logits, "orient"), (proposals, "proposals")):
             _f32c(t, nm)
-        check(lib().glass_box_decode(c_void_p(_dev(cls_logits)), c_void_p(_dev(deltas)), c_void_p(_dev(orient_logits)),
-                                     c_void_p(_dev(proposals)), R, w, c_void_p(_dev(ob)), c_void_p(_dev(fg)),
-                                     c_void_p(_dev(orr)), c_void_p(stream_handle())), "glass_box_decode")
+        check(lib().glass_box_decode(_dev(cls_logits), _dev(deltas), _dev(orient_logits), _dev(proposals), R, w, _dev(ob), _dev(fg),
+                                     _dev(orr), stream_handle()), "glass_box_decode")
     return ob, fg, orr
 
 
@@ -1200,10 +1203,9 @@ def gc_attention_inplace(x: torch.Tensor, heads: int, w_mask, b_mask, w1, b1, ln
     R, H, W, C = x.shape
     P = w1.shape[0]
     if R:
-        check(lib().glass_gc_attention_inplace(
-            c_void_p(_dev(x)), R, H * W, C, int(heads), P, *[c_void_p(_dev(_f32c(t, "w"))) for t in
-                                                           (w_mask, b_mask, w1, b1, ln_g, ln_b, w2, b2)],
-            c_void_p(stream_handle())), "glass_gc_attention_inplace")
+        params = [_dev(_f32c(t, "w")) for t in (w_mask, b_mask, w1, b1, ln_g, ln_b, w2, b2)]
+        check(lib().glass_gc_attention_inplace(_dev(x), R, H * W, C, int(heads), P, *params, stream_handle()),
+              "glass_gc_attention_inplace")
     return x
 
 
@@ -1211,8 +1213,7 @@ def mean_over_h(x: torch.Tensor) -> torch.Tensor:
     _f32c(x, "x")
     R, H, W, C = x.shape
     y = torch.empty((R, W, C), dtype=torch.float32, device=x.device)
-    check(lib().glass_mean_over_h(c_void_p(_dev(x)), c_void_p(_dev(y)), R, H, W, C, c_void_p(stream_handle())),
-          "glass_mean_over_h")
+    check(lib().glass_mean_over_h(_dev(x), _dev(y), R, H, W, C, stream_handle()), "glass_mean_over_h")
     return y
 
 
@@ -1273,7 +1274,7 @@ def _note_handoff_giveup(st: int, owner) -> None:
 def recurrence_test_hook(spin_limit: int = 0, withhold_ticket: int = -1) -> None:
     """TEST HOOK (glass_recurrence_test_hook): bound of the persistent kernels' waits in sweeps (0 = built-in) and the start
     ticket of a workgroup that never publishes (-1 = none); process-wide, for launches issued afterwards."""
-    check(lib().glass_recurrence_test_hook(ctypes.c_int64(int(spin_limit)), int(withhold_ticket)), "glass_recurrence_test_hook")
+    check(lib().glass_recurrence_test_hook(int(spin_limit), int(withhold_ticket)), "glass_recurrence_test_hook")
 
 
 def bilstm_recurrence(xg: torch.Tensor, w_hh_packed: torch.Tensor, hidden: int, mode=None,
@@ -1290,17 +1291,14 @@ def bilstm_recurrence(xg: torch.Tensor, w_hh_packed: torch.Tensor, hidden: int, 
     if mode != "steps":
         nd, ng = (0, 0) if mode == "persistent" else mode
         nbytes = int(lib().glass_bilstm_persistent_workspace_bytes(R, hidden))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=xg.device)
-        check(lib().glass_bilstm_recurrence_persistent(c_void_p(_dev(xg)), c_void_p(_dev(w_hh_packed)), c_void_p(_dev(out)), R, T,
-                                                       hidden, int(nd), int(ng),
-                                                       c_void_p(_dev(_i32(status, "status")) if status is not None else None),
-                                                       c_void_p(_dev(ws)), ctypes.c_int64(nbytes),
-                                                       c_void_p(stream_handle())), "glass_bilstm_recurrence_persistent")
+        ws = _workspace(nbytes, xg.device)
+        check(lib().glass_bilstm_recurrence_persistent(_dev(xg), _dev(w_hh_packed), _dev(out), R, T, hidden, int(nd), int(ng),
+                                                       _opt(None if status is None else _i32(status, "status")), _dev(ws), nbytes,
+                                                       stream_handle()), "glass_bilstm_recurrence_persistent")
         return out
     nbytes = int(lib().glass_bilstm_workspace_bytes(R, hidden))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=xg.device)
-    check(lib().glass_bilstm_recurrence(c_void_p(_dev(xg)), c_void_p(_dev(w_hh_packed)), c_void_p(_dev(out)), R, T, hidden,
-                                        c_void_p(_dev(ws)), ctypes.c_int64(nbytes), c_void_p(stream_handle())),
+    ws = _workspace(nbytes, xg.device)
+    check(lib().glass_bilstm_recurrence(_dev(xg), _dev(w_hh_packed), _dev(out), R, T, hidden, _dev(ws), nbytes, stream_handle()),
           "glass_bilstm_recurrence")
     return out
 
@@ -1311,6 +1309,15 @@ def recurrence_status(reset: bool = True) -> int:
     st = ctypes.c_int(0)
     check(lib().glass_recurrence_status(ctypes.byref(st), int(bool(reset))), "glass_recurrence_status")
     return int(st.value)
+
+
+def _decoder_weights(weights: dict) -> DecoderWeights:
+    """the glass_decoder_weights struct of a decoder's packed device tensors + 'temperature' (every tensor checked)"""
+    w = DecoderWeights()
+    for n in _DECODER_TENSORS:
+        setattr(w, n, _dev(_f32c(weights[n], n)))
+    w.temperature = float(weights["temperature"])
+    return w
 
 
 def attention_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, roi_image: torch.Tensor, num_images: int,
@@ -1325,29 +1332,23 @@ def attention_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, roi_im
     if R == 0:
         return out
     pred = torch.empty((R, max_len), dtype=torch.int32, device=x.device)
-    w = DecoderWeights()
-    for n in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB"):
-        setattr(w, n, _dev(_f32c(weights[n], n)))
-    w.temperature = float(weights["temperature"])
+    w = _decoder_weights(weights)
     mode = _DEFAULT.rnn if mode is None else mode
     if (mode != "steps" and "sW_rm" in weights and "emb_gi" in weights and
             lib().glass_decode_persistent_supported(T, D, int(num_classes), int(max_len))):
         nbytes = int(lib().glass_decode_persistent_workspace_bytes(R))
-        ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-        check(lib().glass_attention_decode_persistent(
-            c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), c_void_p(_dev(_f32c(weights["sW_rm"], "sW_rm"))),
-            c_void_p(_dev(_f32c(weights["emb_gi"], "emb_gi"))), c_void_p(_dev(roi_image)), R, int(num_images), T, D, int(num_classes),
-            int(max_len), int(eos), c_void_p(_dev(out)), c_void_p(_dev(pred)),
-            c_void_p(_dev(_i32(status, "status")) if status is not None else None), c_void_p(_dev(ws)), ctypes.c_int64(nbytes),
-            c_void_p(stream_handle())), "glass_attention_decode_persistent")
+        ws = _workspace(nbytes, x.device)
+        check(lib().glass_attention_decode_persistent(_dev(x), _dev(xproj), ctypes.byref(w), _dev(_f32c(weights["sW_rm"], "sW_rm")),
+                                                      _dev(_f32c(weights["emb_gi"], "emb_gi")), _dev(roi_image), R, int(num_images),
+                                                      T, D, int(num_classes), int(max_len), int(eos), _dev(out), _dev(pred),
+                                                      _opt(None if status is None else _i32(status, "status")), _dev(ws), nbytes,
+                                                      stream_handle()), "glass_attention_decode_persistent")
         return out
     nbytes = int(lib().glass_decode_workspace_bytes(R, D))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    check(lib().glass_attention_decode(c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), c_void_p(_dev(roi_image)),
-                                       R, int(num_images), T, D, int(num_classes), int(max_len), int(eos),
-                                       c_void_p(_dev(out)), c_void_p(_dev(pred)), c_void_p(_dev(ws)), ctypes.c_int64(nbytes),
-                                       c_void_p(stream_handle())),
-          "glass_attention_decode")
+    ws = _workspace(nbytes, x.device)
+    check(lib().glass_attention_decode(_dev(x), _dev(xproj), ctypes.byref(w), _dev(roi_image), R, int(num_images), T, D,
+                                       int(num_classes), int(max_len), int(eos), _dev(out), _dev(pred), _dev(ws), nbytes,
+                                       stream_handle()), "glass_attention_decode")
     return out
 
 
@@ -1362,15 +1363,11 @@ def attention_decode_step(x: torch.Tensor, xproj: torch.Tensor, weights: dict, h
     h_out = torch.empty((R, D), dtype=torch.float32, device=x.device)
     if R == 0:
         return logits, probs, h_out
-    w = DecoderWeights()
-    for n in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB"):
-        setattr(w, n, _dev(_f32c(weights[n], n)))
-    w.temperature = float(weights["temperature"])
+    w = _decoder_weights(weights)
     nbytes = int(lib().glass_decode_step_workspace_bytes(R, D))
-    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    check(lib().glass_attention_decode_step(c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), R, T, D, int(num_classes),
-                                            c_void_p(_dev(h)), c_void_p(_dev(y_prev)), c_void_p(_dev(h_out)), c_void_p(_dev(logits)),
-                                            c_void_p(_dev(probs)), c_void_p(_dev(ws)), ctypes.c_int64(nbytes), c_void_p(stream_handle())),
+    ws = _workspace(nbytes, x.device)
+    check(lib().glass_attention_decode_step(_dev(x), _dev(xproj), ctypes.byref(w), R, T, D, int(num_classes), _dev(h), _dev(y_prev),
+                                            _dev(h_out), _dev(logits), _dev(probs), _dev(ws), nbytes, stream_handle()),
           "glass_attention_decode_step")
     return logits, probs, h_out
 
@@ -1390,16 +1387,11 @@ def beam_search(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width:
     scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
     lengths = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
     path = torch.empty((B, max(L, 0), max(C, 0)), dtype=torch.float32, device=dev) if path_probs else None
-    w = DecoderWeights()
-    for n in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB"):
-        setattr(w, n, _dev(_f32c(weights[n], n)))
-    w.temperature = float(weights["temperature"])
+    w = _decoder_weights(weights)
     nbytes = int(lib().glass_beam_search_workspace_bytes(B, k, T, D, C, L))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-    check(lib().glass_beam_search(c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), B, k, T, D, C, L, int(eos),
-                                  c_void_p(_dev(symbols)), c_void_p(_dev(scores)), c_void_p(_dev(lengths)),
-                                  c_void_p(_dev(path)) if path is not None else None, c_void_p(_dev(ws)),
-                                  ctypes.c_int64(nbytes), c_void_p(stream_handle())), "glass_beam_search")
+    ws = _workspace(nbytes, dev)
+    check(lib().glass_beam_search(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _dev(symbols), _dev(scores),
+                                  _dev(lengths), _opt(path), _dev(ws), nbytes, stream_handle()), "glass_beam_search")
     return (symbols, scores, lengths, path) if path_probs else (symbols, scores, lengths)
 
 
@@ -1428,18 +1420,12 @@ def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: 
     rows = (B, n, max(L, 0), max(C, 0))
     out_probs = torch.empty(rows, dtype=torch.float32, device=dev) if probs else None
     out_logits = torch.empty(rows, dtype=torch.float32, device=dev) if logits else None
-    w = DecoderWeights()
-    for name in ("sW", "sB", "wW", "wB", "emb", "w_ih", "w_hh", "b_ih", "b_hh", "fcW", "fcB"):
-        setattr(w, name, _dev(_f32c(weights[name], name)))
-    w.temperature = float(weights["temperature"])
+    w = _decoder_weights(weights)
     nbytes = int(lib().glass_forced_decode_workspace_bytes(B, n, T, D, C, L))
-    ws = torch.empty((max(nbytes, 16),), dtype=torch.uint8, device=dev)
-    check(lib().glass_forced_decode(c_void_p(_dev(x)), c_void_p(_dev(xproj)), ctypes.byref(w), B, n, T, D, C, L, int(eos),
-                                    c_void_p(_dev(targets)), c_void_p(_dev(lengths)) if lengths is not None else None,
-                                    c_void_p(_dev(step_logp)), c_void_p(_dev(scores)), c_void_p(_dev(out_len)),
-                                    c_void_p(_dev(out_probs)) if out_probs is not None else None,
-                                    c_void_p(_dev(out_logits)) if out_logits is not None else None, c_void_p(_dev(ws)),
-                                    ctypes.c_int64(nbytes), c_void_p(stream_handle())), "glass_forced_decode")
+    ws = _workspace(nbytes, dev)
+    check(lib().glass_forced_decode(_dev(x), _dev(xproj), ctypes.byref(w), B, n, T, D, C, L, int(eos), _dev(targets), _opt(lengths),
+                                    _dev(step_logp), _dev(scores), _dev(out_len), _opt(out_probs), _opt(out_logits), _dev(ws),
+                                    nbytes, stream_handle()), "glass_forced_decode")
     return step_logp, scores, out_len, out_probs, out_logits
 
 
@@ -1459,12 +1445,9 @@ def detections_finalize(boxes: torch.Tensor, scores: torch.Tensor, orient: Optio
     oo = oo if orient is not None else None
     ot = ot if text is not None else None
     _f32c(boxes, "boxes"); _f32c(scores, "scores"); _i32(counts, "counts"); _f32c(scale_xy, "scale_xy"); _i32(out_hw, "out_hw")
-    opt = lambda t: c_void_p(_dev(t)) if t is not None else c_void_p(None)
-    check(lib().glass_detections_finalize(
-        c_void_p(_dev(boxes)), c_void_p(_dev(scores)), opt(orient), opt(text), c_void_p(_dev(counts)), opt(roi_start),
-        c_void_p(_dev(scale_xy)), c_void_p(_dev(out_hw)), N, K, TC, c_float(min_box_dim), int(bool(do_filter_small)),
-        c_void_p(_dev(ob)), c_void_p(_dev(os_)), opt(oo), opt(ot), c_void_p(_dev(oc)), c_void_p(stream_handle())),
-        "glass_detections_finalize")
+    check(lib().glass_detections_finalize(_dev(boxes), _dev(scores), _opt(orient), _opt(text), _dev(counts), _opt(roi_start),
+                                          _dev(scale_xy), _dev(out_hw), N, K, TC, min_box_dim, int(bool(do_filter_small)), _dev(ob),
+                                          _dev(os_), _opt(oo), _opt(ot), _dev(oc), stream_handle()), "glass_detections_finalize")
     return ob, os_, oo, ot, oc
 
 
@@ -1475,8 +1458,7 @@ def text_argmax(text: torch.Tensor, counts: torch.Tensor):
     N, K, T, C = (int(v) for v in text.shape)
     arg = torch.empty((N, K, T), dtype=torch.int32, device=text.device)
     mx = torch.empty((N, K, T), dtype=torch.float32, device=text.device)
-    check(lib().glass_text_argmax(c_void_p(_dev(text)), c_void_p(_dev(counts)), N, K, T, C, c_void_p(_dev(arg)), c_void_p(_dev(mx)),
-                                  c_void_p(stream_handle())), "glass_text_argmax")
+    check(lib().glass_text_argmax(_dev(text), _dev(counts), N, K, T, C, _dev(arg), _dev(mx), stream_handle()), "glass_text_argmax")
     return arg, mx
 
 
@@ -1485,11 +1467,11 @@ def pack_word_records(words: dict, max_det: int, steps: int) -> torch.Tensor:
     N, Kk = words["scores"].shape
     Tw = int(words["char"].shape[2])
     rec = torch.empty((N, 1 + max_det * (16 + steps)), dtype=torch.float32, device=words["scores"].device)
-    check(lib().glass_pack_word_records(c_void_p(_dev(_f32c(words["boxes"], "boxes"))), c_void_p(_dev(_f32c(words["scores"], "scores"))),
-                                        c_void_p(_dev(_f32c(words["text_score"], "text_score"))), c_void_p(_dev(_f32c(words["polygons"], "polygons"))),
-                                        c_void_p(_dev(_i32(words["text_len"], "text_len"))), c_void_p(_dev(_i32(words["char"], "char"))),
-                                        c_void_p(_dev(_i32(words["count"], "count"))), N, Kk, Tw, int(max_det), int(steps),
-                                        c_void_p(_dev(rec)), c_void_p(stream_handle())), "glass_pack_word_records")
+    check(lib().glass_pack_word_records(_dev(_f32c(words["boxes"], "boxes")), _dev(_f32c(words["scores"], "scores")),
+                                        _dev(_f32c(words["text_score"], "text_score")), _dev(_f32c(words["polygons"], "polygons")),
+                                        _dev(_i32(words["text_len"], "text_len")), _dev(_i32(words["char"], "char")),
+                                        _dev(_i32(words["count"], "count")), N, Kk, Tw, int(max_det), int(steps), _dev(rec),
+                                        stream_handle()), "glass_pack_word_records")
     return rec
 
 
@@ -1521,7 +1503,6 @@ def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.T
         out[name] = (v if dt == torch.float32 else v.view(torch.int32)).view(shape)
         off += n
     thr = (c_float * 8)(*[float(v) for v in thresholds8])
-    opt = lambda t: c_void_p(_dev(t)) if t is not None else c_void_p(None)
     arg = mx = None
     if text is not None:
         if T > 64:
@@ -1529,17 +1510,15 @@ def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.T
         arg, mx = text_argmax(text, counts)
     if scale_xy is not None:
         _f32c(scale_xy, "scale_xy")
-    args = (c_void_p(_dev(boxes)), c_void_p(_dev(scores)), c_void_p(_dev(counts)), opt(arg), opt(mx), opt(scale_xy), N, K, T, thr,
-            int(stop_index), c_void_p(_dev(out["boxes"])), c_void_p(_dev(out["scores"])), c_void_p(_dev(out["polygons"])),
-            c_void_p(_dev(out["src"])), c_void_p(_dev(out["char"])), c_void_p(_dev(out["text_score"])),
-            c_void_p(_dev(out["text_len"])), c_void_p(_dev(out["count"])))
+    args = (_dev(boxes), _dev(scores), _dev(counts), _opt(arg), _opt(mx), _opt(scale_xy), N, K, T, thr, int(stop_index),
+            _dev(out["boxes"]), _dev(out["scores"]), _dev(out["polygons"]), _dev(out["src"]), _dev(out["char"]),
+            _dev(out["text_score"]), _dev(out["text_len"]), _dev(out["count"]))
     if K <= POSTPROCESS_LDS_MAX_K:
-        check(lib().glass_postprocess_words(*args, c_void_p(stream_handle())), "glass_postprocess_words")
+        check(lib().glass_postprocess_words(*args, stream_handle()), "glass_postprocess_words")
     else:
         ws_bytes = int(lib().glass_postprocess_words_dense_workspace_bytes(N, K))
-        ws = torch.empty(((ws_bytes + 15) // 16 * 4,), dtype=torch.int32, device=dev)     # needs no initialisation
-        check(lib().glass_postprocess_words_dense(*args, c_void_p(_dev(ws)), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())),
-              "glass_postprocess_words_dense")
+        ws = _workspace(ws_bytes, dev)                   # needs no initialisation
+        check(lib().glass_postprocess_words_dense(*args, _dev(ws), ws_bytes, stream_handle()), "glass_postprocess_words_dense")
     return out
 
 
@@ -1592,11 +1571,10 @@ def lexicon_match(queries: Sequence[bytes], segments: Sequence[int], word_off: t
     q_seg = upload(np.asarray(segments, dtype=np.int32), torch.int32, dev)
     L_ = lib()
     ws_bytes = int(L_.glass_lexicon_match_workspace_bytes(Q))
-    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
-    check(L_.glass_lexicon_match(c_void_p(_dev(q_sym)), c_void_p(_dev(q_len)), c_void_p(_dev(q_seg)), Q, c_void_p(_dev(word_off)),
-                                 c_void_p(_dev(word_len)), c_void_p(_dev(word_sym)), c_void_p(_dev(word_index)), L,
-                                 c_void_p(_dev(seg_off)), S, int(max_segment_words), c_void_p(_dev(index)), c_void_p(_dev(dist)),
-                                 c_void_p(_dev(ws)), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_lexicon_match")
+    ws = _workspace(ws_bytes, dev)
+    check(L_.glass_lexicon_match(_dev(q_sym), _dev(q_len), _dev(q_seg), Q, _dev(word_off), _dev(word_len), _dev(word_sym),
+                                 _dev(word_index), L, _dev(seg_off), S, int(max_segment_words), _dev(index), _dev(dist), _dev(ws),
+                                 ws_bytes, stream_handle()), "glass_lexicon_match")
     return index, dist
 
 
@@ -1606,7 +1584,7 @@ def lexicon_match_weighted_launch(q_sym, q_len, q_seg, cost, cost_doubles, cost_
     Q, L, S = int(q_len.numel()), int(word_off.numel()), int(seg_off.numel()) - 1
     L_ = lib()
     ws_bytes = int(L_.glass_lexicon_match_weighted_workspace_bytes(Q, int(max_segment_words)))
-    ws = torch.empty((max(ws_bytes // 8, 1),), dtype=torch.int64, device=word_off.device)
+    ws = _workspace(ws_bytes, word_off.device)
     check(L_.glass_lexicon_match_weighted(
         _dev(q_sym), _dev(q_len), _dev(q_seg), Q, _dev(cost), int(cost_doubles), _dev(cost_off), _dev(sym_class), int(n_classes),
         int(max_query_len), _dev(word_off), _dev(word_len), _dev(word_sym), _dev(word_index), L, _dev(seg_off), S,
@@ -1699,11 +1677,10 @@ def rrc_pair_areas(pts: torch.Tensor, poly_off: torch.Tensor, gt_off: torch.Tens
         return area, inter
     L_ = lib()
     ws_bytes = int(L_.glass_rrc_pair_areas_workspace_bytes(n_poly))
-    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
-    check(L_.glass_rrc_pair_areas(c_void_p(pts.data_ptr()), ctypes.c_int64(int(pts.shape[0])), c_void_p(poly_off.data_ptr()), n_poly,
-                                  c_void_p(gt_off.data_ptr()), c_void_p(det_off.data_ptr()), c_void_p(pair_off.data_ptr()), n_images,
-                                  ctypes.c_int64(int(n_pairs)), c_void_p(area.data_ptr()), c_void_p(inter.data_ptr()),
-                                  c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_rrc_pair_areas")
+    ws = _workspace(ws_bytes, dev)
+    check(L_.glass_rrc_pair_areas(pts.data_ptr(), int(pts.shape[0]), poly_off.data_ptr(), n_poly, gt_off.data_ptr(),
+                                  det_off.data_ptr(), pair_off.data_ptr(), n_images, int(n_pairs), area.data_ptr(),
+                                  inter.data_ptr(), ws.data_ptr(), ws_bytes, stream_handle()), "glass_rrc_pair_areas")
     return area, inter
 
 
@@ -1733,13 +1710,12 @@ def rrc_match(area: torch.Tensor, inter: torch.Tensor, pair_off: torch.Tensor, g
         return det_dc_e2e, det_dc_det, match_e2e, match_det
     L_ = lib()
     ws_bytes = int(L_.glass_rrc_match_workspace_bytes(n_det))
-    ws = torch.empty((max(ws_bytes, 8) // 8,), dtype=torch.int64, device=dev)
-    check(L_.glass_rrc_match(c_void_p(area.data_ptr()), int(area.numel()), c_void_p(inter.data_ptr()), ctypes.c_int64(int(inter.numel())),
-                             c_void_p(pair_off.data_ptr()), c_void_p(gt_off.data_ptr()), c_void_p(det_off.data_ptr()), n_images,
-                             c_void_p(gt_dontcare_e2e.data_ptr()), c_void_p(gt_dontcare_det.data_ptr()), n_gt, n_det,
-                             c_void_p(det_dc_e2e.data_ptr()), c_void_p(det_dc_det.data_ptr()), c_void_p(match_e2e.data_ptr()),
-                             c_void_p(match_det.data_ptr()), c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes),
-                             c_void_p(stream_handle())), "glass_rrc_match")
+    ws = _workspace(ws_bytes, dev)
+    check(L_.glass_rrc_match(area.data_ptr(), int(area.numel()), inter.data_ptr(), int(inter.numel()), pair_off.data_ptr(),
+                             gt_off.data_ptr(), det_off.data_ptr(), n_images, gt_dontcare_e2e.data_ptr(),
+                             gt_dontcare_det.data_ptr(), n_gt, n_det, det_dc_e2e.data_ptr(), det_dc_det.data_ptr(),
+                             match_e2e.data_ptr(), match_det.data_ptr(), ws.data_ptr(), ws_bytes, stream_handle()),
+          "glass_rrc_match")
     return det_dc_e2e, det_dc_det, match_e2e, match_det
 
 
@@ -1781,16 +1757,14 @@ def rrc_sweep(area: torch.Tensor, inter: torch.Tensor, pair_off: torch.Tensor, g
     if max_dets is None:
         max_dets = int((det_off[1:] - det_off[:-1]).max())
     L_ = lib()
-    ws_bytes = int(L_.glass_rrc_sweep_workspace_bytes(n_images, n_gt, n_det, ctypes.c_int64(int(inter.numel())), int(max_dets), n_comb))
-    ws = torch.empty((max(ws_bytes, 16) // 8,), dtype=torch.int64, device=area.device)
-    check(L_.glass_rrc_sweep(c_void_p(area.data_ptr()), int(area.numel()), c_void_p(inter.data_ptr()), ctypes.c_int64(int(inter.numel())),
-                             c_void_p(pair_off.data_ptr()), c_void_p(gt_off.data_ptr()), c_void_p(det_off.data_ptr()), n_images,
-                             c_void_p(gt_dontcare_e2e.data_ptr()), c_void_p(gt_dontcare_det.data_ptr()), n_gt,
-                             c_void_p(det_dontcare_e2e.data_ptr()), c_void_p(det_dontcare_det.data_ptr()),
-                             c_void_p(det_score_text.data_ptr()), c_void_p(det_score_det.data_ptr()), n_det, int(max_dets),
-                             c_void_p(gt_accept.data_ptr()), c_void_p(det_word.data_ptr()), c_void_p(text_th.data_ptr()),
-                             c_void_p(det_th.data_ptr()), n_comb, c_void_p(counts.data_ptr()), c_void_p(ws.data_ptr()),
-                             ctypes.c_int64(ws_bytes), c_void_p(stream_handle())), "glass_rrc_sweep")
+    ws_bytes = int(L_.glass_rrc_sweep_workspace_bytes(n_images, n_gt, n_det, int(inter.numel()), int(max_dets), n_comb))
+    ws = _workspace(ws_bytes, area.device)
+    check(L_.glass_rrc_sweep(area.data_ptr(), int(area.numel()), inter.data_ptr(), int(inter.numel()), pair_off.data_ptr(),
+                             gt_off.data_ptr(), det_off.data_ptr(), n_images, gt_dontcare_e2e.data_ptr(),
+                             gt_dontcare_det.data_ptr(), n_gt, det_dontcare_e2e.data_ptr(), det_dontcare_det.data_ptr(),
+                             det_score_text.data_ptr(), det_score_det.data_ptr(), n_det, int(max_dets), gt_accept.data_ptr(),
+                             det_word.data_ptr(), text_th.data_ptr(), det_th.data_ptr(), n_comb, counts.data_ptr(), ws.data_ptr(),
+                             ws_bytes, stream_handle()), "glass_rrc_sweep")
     return counts
 
 
@@ -1817,24 +1791,23 @@ def mask_rings(masks: torch.Tensor):
     if not (1 <= H <= 65535 and 1 <= W <= 65535 and H * W < 2 ** 31):
         raise GlassLibraryError(f"masks of {H} x {W}: H, W must be in 1..65535 and H * W < 2^31")
     L_ = lib()
-    st = c_void_p(stream_handle())
+    st = stream_handle()
     win = torch.empty((R, 4), dtype=torch.int32, device=dev)
-    check(L_.glass_mask_windows(c_void_p(masks.data_ptr()), R, H, W, c_void_p(win.data_ptr()), st), "glass_mask_windows")
+    check(L_.glass_mask_windows(masks.data_ptr(), R, H, W, win.data_ptr(), st), "glass_mask_windows")
     win_host = win.cpu()                                               # the host waits: the windows size the workspace
-    ws_bytes = int(L_.glass_mask_rings_workspace_bytes(c_void_p(win_host.data_ptr()), R, H, W))
+    ws_bytes = int(L_.glass_mask_rings_workspace_bytes(win_host.data_ptr(), R, H, W))
     ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
     meta = torch.empty((R + 2,), dtype=torch.int32, device=dev)        # ring_off [R + 1] | status
-    status = c_void_p(meta.data_ptr() + 4 * (R + 1))
-    check(L_.glass_mask_rings_count(c_void_p(masks.data_ptr()), R, H, W, c_void_p(win.data_ptr()), c_void_p(ws.data_ptr()),
-                                    ctypes.c_int64(ws_bytes), c_void_p(meta.data_ptr()), status, st), "glass_mask_rings_count")
+    status = meta.data_ptr() + 4 * (R + 1)
+    check(L_.glass_mask_rings_count(masks.data_ptr(), R, H, W, win.data_ptr(), ws.data_ptr(), ws_bytes, meta.data_ptr(), status,
+                                    st), "glass_mask_rings_count")
     total, code = (int(v) for v in meta[R:].cpu())                     # the host waits: the vertex total sizes xy
     if code != 0:
         raise GlassLibraryError(f"glass_mask_rings_count: status {code} (2 short workspace, 3 unclosed walk, 4 too many vertices)")
     xy = torch.empty((total, 2), dtype=torch.int32, device=dev)
     if total:
-        check(L_.glass_mask_rings_write(R, H, W, c_void_p(win.data_ptr()), c_void_p(ws.data_ptr()), ctypes.c_int64(ws_bytes),
-                                        c_void_p(meta.data_ptr()), c_void_p(xy.data_ptr()), ctypes.c_int64(total), status, st),
-              "glass_mask_rings_write")
+        check(L_.glass_mask_rings_write(R, H, W, win.data_ptr(), ws.data_ptr(), ws_bytes, meta.data_ptr(), xy.data_ptr(), total,
+                                        status, st), "glass_mask_rings_write")
     return xy, meta[:R + 1]
 
 
@@ -1879,7 +1852,6 @@ def ring_check(pts: torch.Tensor, ring_off_host):
     n_tasks = int(task_off[-1])
     dev_off = upload(off, torch.int32, dev)
     dev_task = upload(task_off, torch.int64, dev)
-    check(lib().glass_ring_check(c_void_p(pts.data_ptr()), ctypes.c_int64(P), c_void_p(dev_off.data_ptr()), n_rings,
-                                 c_void_p(dev_task.data_ptr()), ctypes.c_int64(n_tasks), c_void_p(verdict.data_ptr()),
-                                 c_void_p(area2.data_ptr()), c_void_p(stream_handle())), "glass_ring_check")
+    check(lib().glass_ring_check(pts.data_ptr(), P, dev_off.data_ptr(), n_rings, dev_task.data_ptr(), n_tasks, verdict.data_ptr(),
+                                 area2.data_ptr(), stream_handle()), "glass_ring_check")
     return verdict, area2
