@@ -11,6 +11,7 @@
 // (packed[k/4][row][4]) so that the 64 lanes of a wavefront read 1 KiB contiguous per load; reductions (softmax,
 // LayerNorm, attention energies) are wavefront shuffle reductions (64 lanes) + one LDS hop across the 4 wavefronts.
 #include "recognition_common.h"
+#include "glass_hip_ext.h"
 
 // acc[g][r] += sum_k W[g*gstride + u][k] * vec[r][k] for one output unit `u` per thread, weights in the
 // k-blocked layout (w4[k4 * rows_total + row] = 4 consecutive k of `row`).  L2 latency (~300 ns) is far
@@ -1145,5 +1146,312 @@ extern "C" int glass_forced_decode(const float* x, const float* xproj, const gla
     forced_step(hb[(step + 1) & 1], step);
   }
   GLASS_CHECK_LAUNCH("glass_forced_decode");
+  return GLASS_OK;
+}
+
+// ================================================================== lexicon-constrained beam search (glass_hip_ext.h)
+// glass_beam_search with a mask: every slot carries a node of the lexicon's trie, a candidate (beam, class) keeps its score
+// only where the node has a child for the class's fold symbol (or, for <eos>, where a word ends at the node), and the
+// finalisation returns the k best COMPLETED words.  The step arithmetic (rows_fc, row_lsm, rows_attend, the k-round top-k,
+// dec_gru_kernel) is the unconstrained search's, element for element.
+//   workspace: that of glass_beam_search | node table [B,L,k] (the slot's node after the step; -1 = dead)
+struct LexParams {
+  const unsigned* child_mask;       // [N][MW]
+  const int* child_base;            // [N]
+  const int* node_word;             // [N]
+  const int* seg_root;              // [S]
+  const int* fold;                  // [C]
+  const int* item_segment;          // [B]
+  int* nd;                          // workspace [B][L][k]
+  int N, S, F, MW;
+};
+
+// beam_step_kernel with the mask.  Thread u owns class u: its k mask words (one per beam) are loaded once per step into the
+// bit set `allow`; the k node ids live in LDS.  After the selection, thread j moves slot j to its child node.
+template <int KB>
+__global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams bp, LexParams lp, const float* __restrict__ hraw,
+                                                       int step) {
+  __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
+  __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
+  __shared__ float cand[KB][DEC_CMAX];
+  __shared__ float energy[KB][DEC_TMAX];
+  __shared__ float run[KB], ssel[KB];
+  __shared__ int ysel[KB], psel[KB], snode[KB];
+  __shared__ float wbest[2][4];
+  __shared__ int wbesti[2][4];
+  const int u = threadIdx.x, lane = u & 63, wave = u >> 6;
+  const int b = blockIdx.x;
+  const int C = p.C, k = bp.k, L = bp.L;
+  const long row0 = (long)b * k;
+#pragma unroll
+  for (int r = 0; r < KB; ++r) h[r][u] = (step >= 0 && r < k) ? hraw[(row0 + r) * DEC_D + u] : 0.f;
+  if (u < KB) {
+    ysel[u] = 0;
+    psel[u] = 0;
+    ssel[u] = -INFINITY;
+    float rs = -INFINITY;
+    int node = -1;
+    if (u < k) {
+      if (step <= 0) {
+        if (u == 0) {
+          rs = 0.f;
+          const int seg = lp.item_segment[b];
+          if (seg >= 0 && seg < lp.S) node = lp.seg_root[seg];
+        }
+      } else {
+        const long i = ((long)b * L + (step - 1)) * k + u;
+        rs = bp.sc[i];
+        node = bp.sy[i] == bp.eos ? -1 : lp.nd[i];
+      }
+      if (node < 0 || node >= lp.N) { node = -1; rs = -INFINITY; }      // a dead slot: no node, never finite again
+    }
+    run[u] = rs;
+    snode[u] = node;
+  }
+  __syncthreads();
+  if (step >= 0) {
+    // ---- the mask of class u against the k nodes: bit r of `allow` = candidate (beam r, class u) may be emitted
+    unsigned allow = 0u;
+    if (u < C) {
+      const bool stop = u == bp.eos;
+      const int f = lp.fold[u];
+      const bool sym = !stop && f >= 0 && f < lp.F;
+#pragma unroll
+      for (int r = 0; r < KB; ++r) {
+        const int node = r < k ? snode[r] : -1;
+        if (node >= 0) {
+          unsigned bit = 0u;
+          if (stop) bit = lp.node_word[node] >= 0 ? 1u : 0u;
+          else if (sym) bit = (lp.child_mask[(long)node * lp.MW + (f >> 5)] >> (f & 31)) & 1u;
+          allow |= bit << r;
+        }
+      }
+    }
+    // ---- logits = fc(h) * temperature
+    rows_fc<KB>(p, C, u, h, cand);
+    __syncthreads();
+    // ---- candidate score = running score + log-softmax (x - max - log(sum exp(x - max))), wavefront per beam
+    for (int r = wave; r < k; r += 4) {
+      float v[DEC_CMAX / 64];
+      float m;
+      const float ls = row_lsm(cand[r], C, lane, v, m), rs = run[r];
+#pragma unroll
+      for (int i = 0; i < DEC_CMAX / 64; ++i) {
+        const int cidx = lane + 64 * i;
+        if (cidx < C) cand[r][cidx] = rs + ((v[i] - m) - ls);
+      }
+    }
+    __syncthreads();
+    // ---- top k of the k*C masked candidates: k rounds of (max score, then min flat index); thread u owns class u of every beam
+    unsigned taken = 0u;
+    for (int j = 0; j < k; ++j) {
+      float best = -INFINITY;
+      int besti = 0x7fffffff;
+      if (u < C) {
+#pragma unroll
+        for (int r = 0; r < KB; ++r) {
+          if (r < k && !((taken >> r) & 1u)) {
+            const float v = ((allow >> r) & 1u) ? cand[r][u] : -INFINITY;
+            if (besti == 0x7fffffff || v > best) { best = v; besti = r * C + u; }
+          }
+        }
+      }
+      wave_argmax_first(best, besti);
+      if (lane == 0) { wbest[j & 1][wave] = best; wbesti[j & 1][wave] = besti; }
+      __syncthreads();
+      float gb = wbest[j & 1][0];
+      int gi = wbesti[j & 1][0];
+#pragma unroll
+      for (int w = 1; w < 4; ++w) {
+        const float vb = wbest[j & 1][w];
+        const int vi = wbesti[j & 1][w];
+        if (vi != 0x7fffffff && (gi == 0x7fffffff || vb > gb || (vb == gb && vi < gi))) { gb = vb; gi = vi; }
+      }
+      // k <= C: a candidate is always left and gi is a real index - unless the logits hold NaN (outside the contract):
+      // the tables must still hold valid slots and classes, they index memory in the later steps and in the finalisation
+      if (gi == 0x7fffffff) gi = j;
+      const int beam = gi / C, cls = gi - beam * C;
+      if (u == cls) taken |= 1u << beam;
+      if (u == 0) {
+        const long i = ((long)b * L + step) * k + j;
+        bp.sc[i] = gb; bp.pr[i] = beam; bp.sy[i] = cls;
+        ysel[j] = cls; psel[j] = beam; ssel[j] = gb;
+      }
+    }
+    __syncthreads();
+    // ---- slot j follows its symbol into the trie: the child node, the node itself for <eos> (the terminal node, whose word
+    // the finalisation reports), no node for a selected -inf candidate or an index outside the arrays
+    if (u < k) {
+      const int cls = ysel[u], par = snode[psel[u]];
+      int node = -1;
+      if (ssel[u] > -INFINITY && par >= 0) {
+        if (cls == bp.eos) node = par;
+        else {
+          const int f = lp.fold[cls];
+          if (f >= 0 && f < lp.F) {
+            const unsigned* mw = lp.child_mask + (long)par * lp.MW;
+            const int wq = f >> 5;
+            int below = 0;
+            for (int q = 0; q < wq; ++q) below += __popc(mw[q]);
+            below += __popc(mw[wq] & ((1u << (f & 31)) - 1u));
+            const long child = (long)lp.child_base[par] + below;
+            if (child >= 0 && child < lp.N) node = (int)child;
+          }
+        }
+      }
+      lp.nd[((long)b * L + step) * k + u] = node;
+    }
+    if (step + 1 >= L) return;
+    __syncthreads();
+    // ---- states follow their predecessors (in place: column u of every row passes through registers)
+    float hv[KB];
+#pragma unroll
+    for (int r = 0; r < KB; ++r) hv[r] = r < k ? h[psel[r]][u] : 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int r = 0; r < KB; ++r) {
+      h[r][u] = hv[r];
+      if (r < k) bp.hsel[(row0 + r) * DEC_D + u] = hv[r];
+    }
+    __syncthreads();
+  }
+  rows_attend<KB>(p, b, k, row0, u, h, sproj, energy, ysel);
+}
+
+// The k best completed entries of one item, one wavefront per item: an entry (t, slot) is completed when its symbol is <eos>
+// and its score finite; order = score descending, then flat index t*k + slot ascending (t, then slot).  Lane l owns the
+// entries l + 64 i; k rounds of the wavefront arg-max, then lane r walks result r back through the predecessor table.
+__global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams lp, int C, int* __restrict__ out_sym,
+                                                       float* __restrict__ out_sc, int* __restrict__ out_len,
+                                                       int* __restrict__ out_word, float* __restrict__ out_path) {
+  __shared__ float sc[BEAM_LMAX * BEAM_KMAX];
+  __shared__ int pr[BEAM_LMAX * BEAM_KMAX], sy[BEAM_LMAX * BEAM_KMAX], nd[BEAM_LMAX * BEAM_KMAX];
+  __shared__ int res[BEAM_KMAX];
+  __shared__ int p_idx[BEAM_LMAX];            // the slots of result 0 along its ancestor chain
+  const int b = blockIdx.x, lane = threadIdx.x, k = bp.k, L = bp.L, n = L * k;
+  for (int i = lane; i < n; i += 64) {
+    sc[i] = bp.sc[(long)b * n + i];
+    pr[i] = bp.pr[(long)b * n + i];
+    sy[i] = bp.sy[(long)b * n + i];
+    nd[i] = lp.nd[(long)b * n + i];
+  }
+  __syncthreads();
+  unsigned taken = 0u;
+  for (int j = 0; j < k; ++j) {
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < BEAM_LMAX * BEAM_KMAX / 64; ++i) {
+      const int e = lane + 64 * i;
+      if (e < n && !((taken >> i) & 1u) && sy[e] == bp.eos) {
+        const float v = sc[e];
+        if (v > -INFINITY && v < INFINITY && (besti == 0x7fffffff || v > best)) { best = v; besti = e; }
+      }
+    }
+    wave_argmax_first(best, besti);
+    if (besti != 0x7fffffff && (besti & 63) == lane) taken |= 1u << (besti >> 6);
+    if (lane == 0) res[j] = besti == 0x7fffffff ? -1 : besti;
+  }
+  __syncthreads();
+  if (lane < k) {
+    const long row = (long)b * k + lane;
+    int* os = out_sym + row * L;
+    const int e = res[lane];
+    if (e < 0) {
+      for (int t = 0; t < L; ++t) os[t] = bp.eos;
+      out_sc[row] = -INFINITY;
+      out_len[row] = 0;
+      out_word[row] = -1;
+    } else {
+      const int t0 = e / k;
+      int slot = e - t0 * k;
+      const int node = nd[e];
+      out_sc[row] = sc[e];
+      out_len[row] = t0 + 1;
+      out_word[row] = (node >= 0 && node < lp.N) ? lp.node_word[node] : -1;
+      for (int t = L - 1; t > t0; --t) os[t] = bp.eos;
+      for (int t = t0; t >= 0; --t) {
+        os[t] = sy[t * k + slot];
+        if (lane == 0) p_idx[t] = slot;
+        slot = min(max(pr[t * k + slot], 0), k - 1);
+      }
+    }
+  }
+  if (out_path == nullptr) return;
+  float* op = out_path + (long)b * L * C;
+  for (int i = lane; i < L * C; i += 64) op[i] = 0.f;
+  __syncthreads();
+  const int e0 = res[0];
+  if (e0 >= 0 && lane <= e0 / k) {
+    const int t = lane;
+    const float cur = sc[t * k + p_idx[t]];
+    const float prev = t > 0 ? sc[(t - 1) * k + p_idx[t - 1]] : 0.f;
+    op[(long)t * C + sy[t * k + p_idx[t]]] = expf(cur - prev);
+  }
+}
+
+extern "C" int64_t glass_beam_search_lexicon_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
+  return glass_beam_search_workspace_bytes(B, k, T, D, C, max_len) + (int64_t)((size_t)B * max_len * k * sizeof(int));
+}
+
+extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
+                                         int D, int C, int max_len, int eos, const uint32_t* child_mask, const int* child_base,
+                                         const int* node_word, const int* seg_root, const int* fold, int N, int S, int F,
+                                         const int* item_segment, int* out_symbols, float* out_scores, int* out_lengths,
+                                         int* out_words, float* out_path_probs, void* workspace, int64_t workspace_bytes,
+                                         glass_stream_t stream) {
+  GLASS_CHECK_ARG(D == DEC_D && T > 0 && T <= DEC_TMAX && C > 0 && C <= DEC_CMAX && k >= 1 && k <= BEAM_KMAX && k <= C &&
+                      max_len >= 1 && max_len <= BEAM_LMAX && B >= 0,
+                  "glass_beam_search_lexicon: needs D=256, 1<=T<=64, 1<=C<=256, 1<=k<=16, k<=C, 1<=max_len<=64, B>=0 "
+                  "(got B=%d k=%d T=%d D=%d C=%d max_len=%d)", B, k, T, D, C, max_len);
+  GLASS_CHECK_ARG(N >= 1 && S >= 1 && F >= 1 && F <= 256, "glass_beam_search_lexicon: needs N>=1, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)",
+                  N, S, F);
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && out_words && workspace,
+                  "glass_beam_search_lexicon: null pointer");
+  GLASS_CHECK_ARG(child_mask && child_base && node_word && seg_root && fold && item_segment,
+                  "glass_beam_search_lexicon: null trie array");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len),
+                  "glass_beam_search_lexicon: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * k;
+  DecParams p;
+  p.x = x; p.xproj = xproj; p.sW = w->sW; p.sB = w->sB; p.wW = w->wW; p.wB = w->wB; p.emb = w->emb; p.w_ih = w->w_ih;
+  p.w_hh = w->w_hh; p.b_ih = w->b_ih; p.b_hh = w->b_hh; p.fcW = w->fcW; p.fcB = w->fcB; p.temperature = w->temperature;
+  p.R = (int)rows; p.T = T; p.C = C; p.max_len = max_len; p.out = nullptr; p.pred = nullptr; p.yprev = nullptr; p.logits = nullptr;
+  float* ws = static_cast<float*>(workspace);
+  float* hsel = ws;
+  float* hraw = ws + rows * D;
+  p.h0 = hsel; p.h1 = hraw; p.inp = ws + rows * D * 2;
+  BeamParams bp;
+  bp.sc = ws + rows * D * 4;
+  bp.pr = reinterpret_cast<int*>(bp.sc + (size_t)B * max_len * k);
+  bp.sy = bp.pr + (size_t)B * max_len * k;
+  bp.hsel = hsel; bp.k = k; bp.L = max_len; bp.eos = eos;
+  LexParams lp;
+  lp.child_mask = child_mask; lp.child_base = child_base; lp.node_word = node_word; lp.seg_root = seg_root; lp.fold = fold;
+  lp.item_segment = item_segment; lp.nd = bp.sy + (size_t)B * max_len * k;
+  lp.N = N; lp.S = S; lp.F = F; lp.MW = (F + 31) / 32;
+  hipError_t e = hipMemsetAsync(hsel, 0, rows * D * sizeof(float), s);           // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_beam_search_lexicon: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B), gg(cdiv((long)rows, GRU_RB), DEC_D / GRU_UB);
+  auto lex_step = [&](int step) {
+    if (k == 1) hipLaunchKernelGGL(lex_step_kernel<1>, gb, dim3(256), 0, s, p, bp, lp, hraw, step);
+    else if (k == 2) hipLaunchKernelGGL(lex_step_kernel<2>, gb, dim3(256), 0, s, p, bp, lp, hraw, step);
+    else if (k <= 4) hipLaunchKernelGGL(lex_step_kernel<4>, gb, dim3(256), 0, s, p, bp, lp, hraw, step);
+    else if (k <= 8) hipLaunchKernelGGL(lex_step_kernel<8>, gb, dim3(256), 0, s, p, bp, lp, hraw, step);
+    else hipLaunchKernelGGL(lex_step_kernel<16>, gb, dim3(256), 0, s, p, bp, lp, hraw, step);
+  };
+  lex_step(-1);                                                                   // attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    hipLaunchKernelGGL(dec_gru_kernel, gg, dim3(256), 0, s, p, hsel, hraw);
+    lex_step(step);
+  }
+  GLASS_CHECK_LAUNCH("glass_beam_search_lexicon");
+  hipLaunchKernelGGL(lex_final_kernel, gb, dim3(64), 0, s, bp, lp, C, out_symbols, out_scores, out_lengths, out_words,
+                     out_path_probs);
+  GLASS_CHECK_LAUNCH("glass_beam_search_lexicon(final)");
   return GLASS_OK;
 }

@@ -4,6 +4,10 @@ The header is the one description of the ABI: `signatures()` parses its prototyp
 gives every entry its `restype` / `argtypes` from them - ctypes then converts plain ints, floats and `None`, passes 64-bit
 sizes and device addresses whole, and refuses a wrongly typed argument on the host (`ctypes.ArgumentError`).
 
+Two headers: include/glass_hip.h is closed (its set of prototypes, `EXPORTS`, is pinned by the host tests); an entry point
+added since is declared in include/glass_hip_ext.h, which includes the first, and is listed in `EXT_EXPORTS`.  `lib()`
+requires and binds both sets the same way; additions leave `ABI_VERSION` alone.
+
 The product path has NO CPU fallback: `lib()` raises if the shared object is missing or
 does not export every declared symbol, and every op wrapper raises if its tensors are not
 on a HIP device.
@@ -70,6 +74,23 @@ def signatures(header: Optional[str] = None) -> Dict[str, Tuple[object, list]]:
 
 
 EXPORTS = list(signatures())        # every entry point the header declares, in its order
+
+_EXT_SIGNATURES: Optional[Dict[str, Tuple[object, list]]] = None
+
+
+def ext_signatures() -> Dict[str, Tuple[object, list]]:
+    """`signatures()` of include/glass_hip_ext.h, the header of the entry points added after glass_hip.h was closed"""
+    global _EXT_SIGNATURES
+    if _EXT_SIGNATURES is None:
+        with open(os.path.join(INCLUDE, "glass_hip_ext.h")) as fh:
+            _EXT_SIGNATURES = signatures(fh.read())
+        both = sorted(set(_EXT_SIGNATURES) & set(signatures()))
+        if both:
+            raise GlassLibraryError(f"include/glass_hip_ext.h declares {both} again")
+    return _EXT_SIGNATURES
+
+
+EXT_EXPORTS = list(ext_signatures())        # every entry point include/glass_hip_ext.h declares, in its order
 
 
 # Device code is compiled WITHOUT packed-f32 (v_pk_*_f32) and fma_mix instruction selection.  On MI355X / ROCm 7.2 a VOP3P
@@ -145,10 +166,10 @@ def lib() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(SO_PATH)
-        missing = [s for s in EXPORTS if not hasattr(L, s)]
+        missing = [s for s in EXPORTS + EXT_EXPORTS if not hasattr(L, s)]
         if missing:
             raise GlassLibraryError(f"{SO_PATH} lacks symbols {missing}")
-        for name, (restype, argtypes) in signatures().items():
+        for name, (restype, argtypes) in {**signatures(), **ext_signatures()}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         _LIB = L

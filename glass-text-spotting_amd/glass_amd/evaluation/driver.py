@@ -6,21 +6,39 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 
 def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[[Dict], Dict], writer=None,
-                         batch_size: int = 8) -> List[Dict]:
+                         batch_size: int = 8, lexicon=None, lexicon_key: Optional[Callable[[Dict], object]] = None) -> List[Dict]:
     """Run `model` over `dataset_dicts` and return its per-image outputs in input order.
 
     The reference evaluates one image per call.  Here up to `batch_size` images share a call, grouped by their own padded
     shape (multiple of the backbone's size divisibility) as GlassRunner.run_batch groups them: detectron2 pads a batch to
     its largest image and the pad region is visible to the backbone and the RPN, so only images of one padded shape give
     per-image results that do not depend on the batch.  `writer` (evaluation.TextResultWriter, or anything with
-    `process(inputs, outputs)`) sees every call's inputs and outputs."""
+    `process(inputs, outputs)`) sees every call's inputs and outputs.
+
+    `lexicon` (evaluation.lexicon.LexiconTrie): lexicon-constrained decoding - the recognizer head is switched to the trie
+    (`RecognizerRCNNHeadV3.set_lexicon`, which needs BEAM_WIDTH >= 1) for the run and back to what it had afterwards; every
+    word the model emits is then a word of the lexicon.  `lexicon_key` (mapped input -> key of a dict lexicon, e.g. the
+    image id of the per-image strong lexicons): the segments of a call's images are set right before the call; without it
+    every image decodes against segment 0."""
     assert batch_size >= 1
+    if lexicon is None and lexicon_key is not None:
+        raise ValueError("lexicon_key without a lexicon")
+    head = None
+    if lexicon is not None:
+        import torch
+        from ..ops import native
+        head = model.roi_heads.recognizer_head
+        before = (head.lexicon, head.image_segments)
+        head.set_lexicon(lexicon)
     d = model.backbone.size_divisibility
     outputs: List[Optional[Dict]] = [None] * len(dataset_dicts)
     pending: Dict[tuple, List[tuple]] = {}
 
     def run(group: List[tuple]) -> None:
         inputs = [inp for _, inp in group]
+        if lexicon_key is not None:
+            segments = [lexicon.segment(lexicon_key(inp)) for inp in inputs]
+            head.image_segments = native.upload(segments, torch.int32, lexicon.device)
         outs = list(model(inputs))
         assert len(outs) == len(inputs)
         if writer is not None:
@@ -28,14 +46,18 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
         for (i, _), o in zip(group, outs):
             outputs[i] = o
 
-    for i, dd in enumerate(dataset_dicts):
-        inp = mapper(dd)
-        h, w = model.input_size(inp)
-        key = ((h + d - 1) // d * d, (w + d - 1) // d * d)
-        group = pending.setdefault(key, [])
-        group.append((i, inp))
-        if len(group) >= batch_size:          # run as soon as a group is full: at most batch_size images per shape are held
-            run(pending.pop(key))
-    for group in pending.values():
-        run(group)
+    try:
+        for i, dd in enumerate(dataset_dicts):
+            inp = mapper(dd)
+            h, w = model.input_size(inp)
+            key = ((h + d - 1) // d * d, (w + d - 1) // d * d)
+            group = pending.setdefault(key, [])
+            group.append((i, inp))
+            if len(group) >= batch_size:      # run as soon as a group is full: at most batch_size images per shape are held
+                run(pending.pop(key))
+        for group in pending.values():
+            run(group)
+    finally:
+        if head is not None:
+            head.lexicon, head.image_segments = before
     return outputs

@@ -10,6 +10,9 @@
     TEST.LEXICON_WEIGHTED) through glass_lexicon_match_weighted (csrc/lexicon_weighted.hip): the host turns each record's
     character probabilities into float64 cost tables (`weighted_cost_tables`), the device finds the candidates and runs
     the DP; `TextResultWriter(matcher=..., weighted_ed=True)` uses it.
+  * `LexiconTrie` - the same lexicons as a trie over the decoder's classes, for the OTHER lexicon protocol: decoding that can
+    only emit lexicon words (glass_beam_search_lexicon, `ASTER_V2.beam_decode(lexicon=...)`,
+    `RecognizerRCNNHeadV3.set_lexicon`), where the matchers above repair a word after it was decoded.
 
 Symbols: both sides are upper-cased with `str.upper()` as the reference does (once, at load, for the lexicon: it can
 change a word's length, e.g. 'ß' -> 'SS').  Queries are ASCII (the writer strips other characters first, `de_ascii`);
@@ -317,3 +320,138 @@ class WeightedLexiconMatcher:
                 # the DP returns its integer border untouched when either word is empty, as the host path does
                 out.append((pairs[word], int(d) if (not s or not word) else d))
         return out
+
+
+NO_FOLD_TOKENS = ("[GO]", "[s]", "[UNK]", "[blank]")
+MAX_FOLD = 256                # fold symbols of a trie (8 mask words of 32 bits per node)
+
+
+def fold_table(characters: Sequence[str], eos: int, case_insensitive: bool = True) -> Tuple[np.ndarray, List[str]]:
+    """-> (fold int32 [C], symbols): fold[c] = the fold symbol of class c, numbered densely in class order, and the fold
+    symbols' strings.  The fold symbol of a class is its character upper-cased with `str.upper()` where that is one
+    character (else, and with case_insensitive=False, the character itself); -1 for the special tokens, any other
+    multi-character class and the class `eos`."""
+    fold = np.full(len(characters), -1, dtype=np.int32)
+    ids: Dict[str, int] = {}
+    for c, ch in enumerate(characters):
+        if c == eos or ch in NO_FOLD_TOKENS or len(ch) != 1:
+            continue
+        up = ch.upper() if case_insensitive else ch
+        sym = up if len(up) == 1 else ch
+        fold[c] = ids.setdefault(sym, len(ids))
+    if not 1 <= len(ids) <= MAX_FOLD:
+        raise ValueError(f"{len(ids)} fold symbols (1..{MAX_FOLD})")
+    return fold, list(ids)
+
+
+class LexiconTrie:
+    """A lexicon as a trie over the decoder's classes, built once on the host and kept on the device: what
+    glass_beam_search_lexicon consults at every decoding step (include/glass_hip_ext.h has the layout).
+
+    `lexicon`: a word list (one segment, key None) or a dict {key: word list} (one segment per key), as DeviceLexicon takes
+    them; `text_encoder_or_characters`: a TextEncoder or its list of class strings; `max_len`: the decoder's steps (a word
+    needs one more step than it has characters, for the stop); `eos`: the stop class.  Words are folded as the matchers fold
+    them - `upper()` once at load - or taken as they are with case_insensitive=False; `upper[i]` is word i (position in the
+    concatenation of the segments in file order) upper-cased, as in DeviceLexicon.  A word that is empty, longer than
+    max_len - 1 characters or holds a character without a fold symbol is left out and counted in `skipped`; so every node
+    has a word below it and a hypothesis alive at the last step can only stop.
+
+    numpy arrays (nodes in breadth-first order, a node's children contiguous and ordered by fold symbol): `fold` int32 [C],
+    `child_mask` uint32 [N,MW], `child_base` int32 [N], `node_word` int32 [N] (-1, or the first word that ends there),
+    `seg_root` int32 [S] (-1 = an empty segment); child(node, f) = child_base[node] + popcount(mask bits below f).
+    `tensors` holds them on the device (the mask as int32 bit patterns) with the int "F"."""
+
+    def __init__(self, lexicon: Union[Sequence[str], Dict[object, Sequence[str]]], text_encoder_or_characters, max_len: int,
+                 eos: int, case_insensitive: bool = True, device=None):
+        import time
+        t0 = time.perf_counter()
+        if isinstance(lexicon, dict):
+            self.keys = list(lexicon.keys())
+            lists = [list(lexicon[k]) for k in self.keys]
+        else:
+            self.keys = [None]
+            lists = [list(lexicon)]
+        self._segment = {k: i for i, k in enumerate(self.keys)}
+        characters = list(getattr(text_encoder_or_characters, "character", text_encoder_or_characters))
+        self.num_classes, self.max_len, self.eos = len(characters), int(max_len), int(eos)
+        self.case_insensitive = bool(case_insensitive)
+        if not 0 <= self.eos < self.num_classes:
+            raise ValueError(f"eos {eos} outside [0, {self.num_classes})")
+        self.fold, self.fold_symbols = fold_table(characters, self.eos, self.case_insensitive)
+        self.num_fold = F = len(self.fold_symbols)
+        self.mask_words = MW = (F + 31) // 32
+        uppers = [[w.upper() for w in words] for words in lists]
+        self.upper = [w for words in uppers for w in words]
+        folded = uppers if self.case_insensitive else lists
+        sym_id = {s: i for i, s in enumerate(self.fold_symbols)}
+        self.skipped = {"empty": 0, "too_long": 0, "no_class": 0}
+        # ---- the kept words as rows of fold symbols
+        w_seg, w_idx, w_sym = [], [], []
+        pos = 0
+        for seg, words in enumerate(folded):
+            for j, w in enumerate(words):
+                if not w:
+                    self.skipped["empty"] += 1
+                elif len(w) > self.max_len - 1:
+                    self.skipped["too_long"] += 1
+                else:
+                    ids = [sym_id.get(ch, -1) for ch in w]
+                    if min(ids) < 0:
+                        self.skipped["no_class"] += 1
+                    else:
+                        w_seg.append(seg); w_idx.append(pos + j); w_sym.append(ids)
+            pos += len(words)
+        S, W = len(lists), len(w_sym)
+        w_len = np.fromiter((len(v) for v in w_sym), dtype=np.int64, count=W)
+        depth = int(w_len.max()) if W else 0
+        sym = np.full((W, max(depth, 1)), -1, dtype=np.int64)
+        for i, v in enumerate(w_sym):
+            sym[i, :len(v)] = v
+        w_seg = np.asarray(w_seg, dtype=np.int64)
+        w_idx = np.asarray(w_idx, dtype=np.int64)
+        # ---- level by level: the nodes of depth d + 1 are the distinct (parent, symbol) pairs, in that order
+        self.seg_root = np.full(S, -1, dtype=np.int32)
+        used = np.unique(w_seg)
+        self.seg_root[used] = np.arange(len(used), dtype=np.int32)
+        n = len(used)
+        at = self.seg_root[w_seg].astype(np.int64) if W else np.zeros(0, dtype=np.int64)       # node of every word's prefix
+        masks, bases, words_at = [np.zeros((n, MW), dtype=np.uint32)], [np.zeros(n, dtype=np.int64)], [np.full(n, -1, dtype=np.int64)]
+        level0 = 0
+        for d in range(depth):
+            live = np.nonzero(w_len > d)[0]
+            key, inv = np.unique(at[live] * F + sym[live, d], return_inverse=True)
+            parent, f = key // F - level0, key % F
+            child = n + np.arange(len(key), dtype=np.int64)
+            np.bitwise_or.at(masks[-1], (parent, f >> 5), (np.uint32(1) << (f & 31).astype(np.uint32)))
+            first = np.unique(parent, return_index=True)
+            bases[-1][first[0]] = child[first[1]]
+            at[live] = child[inv.reshape(-1)]
+            end = live[w_len[live] == d + 1]
+            ends = np.full(len(key), np.iinfo(np.int64).max, dtype=np.int64)
+            np.minimum.at(ends, at[end] - n, w_idx[end])
+            ends[ends == np.iinfo(np.int64).max] = -1
+            level0, n = n, n + len(key)
+            masks.append(np.zeros((len(key), MW), dtype=np.uint32)); bases.append(np.zeros(len(key), dtype=np.int64)); words_at.append(ends)
+        if n == 0:                  # no word at all: one node that no root points to, so that no array is empty
+            masks, bases, words_at, n = [np.zeros((1, MW), dtype=np.uint32)], [np.zeros(1, dtype=np.int64)], [np.full(1, -1, dtype=np.int64)], 1
+        if n >= 2 ** 31:
+            raise ValueError(f"lexicon trie of {n} nodes (max 2^31 - 1)")
+        self.num_nodes = n
+        self.child_mask = np.ascontiguousarray(np.concatenate(masks))
+        self.child_base = np.concatenate(bases).astype(np.int32)
+        self.node_word = np.concatenate(words_at).astype(np.int32)
+        self.nbytes = int(self.child_mask.nbytes + self.child_base.nbytes + self.node_word.nbytes + self.seg_root.nbytes + self.fold.nbytes)
+        self.device = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.tensors = {"child_mask": torch.from_numpy(self.child_mask.view(np.int32)).to(self.device),
+                        "child_base": torch.from_numpy(self.child_base).to(self.device),
+                        "node_word": torch.from_numpy(self.node_word).to(self.device),
+                        "seg_root": torch.from_numpy(self.seg_root).to(self.device),
+                        "fold": torch.from_numpy(self.fold).to(self.device), "F": F}
+        self.build_seconds = time.perf_counter() - t0
+
+    def __len__(self) -> int:
+        return len(self.upper)
+
+    def segment(self, key) -> int:
+        """segment number of a key (None for a plain word list); KeyError for an unknown key, as `lexicon[key]`."""
+        return self._segment[key]

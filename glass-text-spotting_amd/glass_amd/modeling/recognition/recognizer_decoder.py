@@ -18,6 +18,10 @@ Forced decoding (`AttentionRecognitionHead.forward`, prediction_aster.py:33-60, 
 runs the decoder with the emitted symbols given (glass_forced_decode, one ABI call, x / xproj not inflated) - the
 log-likelihood of a transcription; `ASTER_V2.forward(features, labels)` is the reference's surface on top of it, and
 `beam_decode(..., distributions=...)` replays the search's hypotheses for their full per-step distributions.
+
+Lexicon-constrained decoding: `beam_decode(..., lexicon=LexiconTrie, segments=...)` is the search restricted to the words of
+a lexicon (glass_beam_search_lexicon, include/glass_hip_ext.h; the reference has no counterpart): the k most likely lexicon
+words under the model, with their log-likelihoods.
 """
 from __future__ import annotations
 
@@ -44,11 +48,14 @@ class _BeamFields(NamedTuple):
 class BeamResult(_BeamFields):
     """`ASTER_V2.beam_decode`: device tensors, hypotheses in final (best first) order.  The tuple keeps its four fields
     (code that unpacks a result or rebuilds one from its fields is unaffected); `distributions` rides as an attribute:
-    float32 full per-step rows, [B, L, C] ("best") / [B, k, L, C] ("all"), default None."""
+    float32 full per-step rows, [B, L, C] ("best") / [B, k, L, C] ("all"), default None.  So does `words` of a
+    lexicon-constrained search: int32 [B, k], the lexicon word of every hypothesis (index into `LexiconTrie.upper`), -1
+    where there is none; default None."""
 
-    def __new__(cls, symbols, scores, lengths, path_probs=None, distributions=None):
+    def __new__(cls, symbols, scores, lengths, path_probs=None, distributions=None, words=None):
         self = super().__new__(cls, symbols, scores, lengths, path_probs)
         self.distributions = distributions
+        self.words = words
         return self
 
 
@@ -216,8 +223,34 @@ class ASTER_V2(InferenceModule):
             out = tuple(o.squeeze(1) if o is not None else None for o in out)
         return ForcedResult(*out)
 
+    def _lexicon_segments(self, trie, segments, B: int, eos: int, device) -> torch.Tensor:
+        """the checks of `beam_decode(lexicon=trie, segments=...)` -> item segments int32 [B] on the device.  Host-given
+        segments are checked before they are uploaded; a device tensor is passed through unread (the kernel gives an item
+        whose segment is out of range no hypothesis)."""
+        for name, have, want in (("classes", trie.num_classes, self.num_classes), ("max_len", trie.max_len, self.max_word_len),
+                                 ("eos", trie.eos, int(eos))):
+            if have != want:
+                raise ValueError(f"beam_decode: the lexicon trie was built for {name} = {have}, the decoder has {want}")
+        S = len(trie.keys)
+        if segments is None:
+            if S != 1:
+                raise ValueError(f"beam_decode: segments=None needs a one-segment lexicon (this one has {S})")
+            return torch.zeros((B,), dtype=torch.int32, device=device)
+        if torch.is_tensor(segments) and segments.device.type != "cpu":
+            if segments.dtype != torch.int32 or tuple(segments.shape) != (B,):
+                raise ValueError(f"beam_decode: device segments must be int32 [B={B}] (got {segments.dtype} {tuple(segments.shape)})")
+            return segments.contiguous()
+        seg = torch.as_tensor(segments)
+        if seg.dtype.is_floating_point or seg.dtype.is_complex or seg.dtype == torch.bool:
+            raise ValueError(f"beam_decode: segments must hold integers (got {seg.dtype})")
+        if tuple(seg.shape) != (B,):
+            raise ValueError(f"beam_decode: segments must be [B={B}] (got {tuple(seg.shape)})")
+        if seg.numel() and (int(seg.min()) < 0 or int(seg.max()) >= S):
+            raise ValueError(f"beam_decode: segments outside [0, {S}) (found {int(seg.min())}..{int(seg.max())})")
+        return K.upload(seg.contiguous(), torch.int32, device)
+
     def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False,
-                    distributions: Optional[str] = None) -> "BeamResult":
+                    distributions: Optional[str] = None, lexicon=None, segments=None) -> "BeamResult":
         """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
         synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
         `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
@@ -227,13 +260,28 @@ class ASTER_V2(InferenceModule):
         `distributions`: "best" / "all" - after the search, ONE forced replay (glass_forced_decode) of hypothesis 0 / of all
         k hypotheses with the search's lengths gives their FULL per-step softmax rows, [B,L,C] / [B,k,L,C]: what a consumer
         that weighs every class of a step needs (the path rows hold one entry per step).  Rows from the length on, and every
-        row of a hypothesis whose score is -inf (its length is replaced by 0, on the device), are zero."""
+        row of a hypothesis whose score is -inf (its length is replaced by 0, on the device), are zero.
+        `lexicon` (evaluation.lexicon.LexiconTrie): the search can only spell words of the lexicon (glass_beam_search_lexicon)
+        - the hypotheses are the k most likely lexicon words of each item's segment, complete ones only, and the result
+        carries `.words` int32 [B,k] (index into `lexicon.upper`; two case variants of a word are two hypotheses with one
+        index).  With fewer than k words the rest have score -inf, length 0, word -1.  `segments`: int32 [B] on the device,
+        a host sequence of segment numbers (checked here), or None = all 0 (a one-segment lexicon only).  ValueError if the
+        trie was built for another number of classes, max_len or eos."""
         if distributions not in (None, "best", "all"):
             raise ValueError(f'beam_decode: distributions must be None, "best" or "all" (got {distributions!r})')
+        if lexicon is None and segments is not None:
+            raise ValueError("beam_decode: segments without a lexicon")
         x = x.contiguous()
         B, T, D = x.shape
+        seg = self._lexicon_segments(lexicon, segments, B, eos, x.device) if lexicon is not None else None
         xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x      # empty batch: empty results
-        out = K.beam_search(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos), path_probs=path_probs)
+        words = None
+        if lexicon is not None:
+            out = K.beam_search_lexicon(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
+                                        lexicon.tensors, seg, path_probs=path_probs)
+            words, out = out[3], out[:3] + out[4:]
+        else:
+            out = K.beam_search(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos), path_probs=path_probs)
         dist = None
         if distributions is not None:
             n = 1 if distributions == "best" else int(beam_width)
@@ -241,7 +289,7 @@ class ASTER_V2(InferenceModule):
             ln = torch.where(torch.isneginf(sc), torch.zeros_like(ln), ln).contiguous()
             dist = K.forced_decode(x, xproj, self.w, sym, ln, self.num_classes, self.max_word_len, int(eos), probs=True)[3]
             dist = dist[:, 0] if distributions == "best" else dist
-        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist)
+        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist, words)
 
     def forward(self, features: torch.Tensor, labels=None, roi_image: Optional[torch.Tensor] = None,
                 num_images: int = 1, rnn=None, status=None) -> torch.Tensor:

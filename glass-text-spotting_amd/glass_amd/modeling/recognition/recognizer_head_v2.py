@@ -53,6 +53,38 @@ class RecognizerRCNNHeadV3(InferenceModule):
         self.encoder.import_weights(sd, device, prefix + "encoder.")
         self.decoder.import_weights(sd, device, prefix + "decoder.")
 
+    lexicon = None            # set_lexicon: the LexiconTrie the search is constrained to
+    image_segments = None     # set_lexicon: int32 [num_images] on the device, the lexicon segment of every image of a call
+
+    def set_lexicon(self, trie, image_segments=None) -> None:
+        """Constrain the decoding to a lexicon (evaluation.lexicon.LexiconTrie; None switches it off): every RoI decodes to
+        the most likely word of its image's segment (glass_beam_search_lexicon), handed on as path rows exactly as the
+        unconstrained search's - a RoI for which no word completes gets all-zero rows (an empty text with score 0).
+        `image_segments`: int32 [num_images] on the device (default: segment 0 for every image); it is gathered by the
+        RoIs' image ids on the device.  ValueError unless BEAM_WIDTH >= 1, and if the trie does not fit the decoder."""
+        if trie is None:
+            self.lexicon = self.image_segments = None
+            return
+        if self.beam_width < 1:
+            raise ValueError(f"set_lexicon needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 (got {self.beam_width}): the greedy "
+                             "decoder does not search")
+        for name, have, want in (("classes", trie.num_classes, self.decoder.num_classes), ("max_len", trie.max_len, self.decoder.max_word_len),
+                                 ("eos", trie.eos, self.beam_eos)):
+            if have != want:
+                raise ValueError(f"set_lexicon: the lexicon trie was built for {name} = {have}, the head has {want}")
+        if image_segments is not None:
+            if (not torch.is_tensor(image_segments) or image_segments.device.type == "cpu" or image_segments.dtype != torch.int32
+                    or image_segments.dim() != 1):
+                raise ValueError("set_lexicon: image_segments must be an int32 [num_images] tensor on the device")
+        self.lexicon, self.image_segments = trie, image_segments
+
+    def _roi_segments(self, roi_image: torch.Tensor, num_images: int) -> torch.Tensor:
+        if self.image_segments is None:
+            return torch.zeros_like(roi_image)
+        if self.image_segments.shape[0] < num_images:
+            raise ValueError(f"image_segments of {self.image_segments.shape[0]} images for a call of {num_images}")
+        return self.image_segments.index_select(0, roi_image.long()).contiguous()
+
     rnn_override = None       # "steps" once K.HandoffGuard.STICKY_AFTER hand-off give-ups were seen by this head
     rnn_giveups = 0
 
@@ -73,10 +105,11 @@ class RecognizerRCNNHeadV3(InferenceModule):
         def run(rnn, status):
             enc = self.encoder.forward_nhwc(f, rnn=rnn, status=status)
             if self.beam_width > 0:         # the search has no in-kernel hand-off: only the encoder is guarded
+                lex = {} if self.lexicon is None else {"lexicon": self.lexicon, "segments": self._roi_segments(roi_image, num_images)}
                 if self.beam_distributions:
-                    r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best")
+                    r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best", **lex)
                     return r.path_probs, r.distributions
-                return self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True).path_probs
+                return self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, **lex).path_probs
             return self.decoder(enc, roi_image=roi_image, num_images=num_images, rnn=rnn, status=status)
         if self.rnn_override == "steps":
             return run("steps", None)

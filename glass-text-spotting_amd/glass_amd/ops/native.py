@@ -1395,6 +1395,60 @@ def beam_search(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width:
     return (symbols, scores, lengths, path) if path_probs else (symbols, scores, lengths)
 
 
+def beam_search_lexicon(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
+                        eos: int, trie: dict, item_segment: torch.Tensor, path_probs: bool = False):
+    """the beam search constrained to a lexicon (glass_beam_search_lexicon): as `beam_search`, plus `trie` - the device tensors
+    child_mask int32 [N,MW] (the 32-bit mask words), child_base / node_word int32 [N], seg_root int32 [S], fold int32 [C] and
+    the int F (evaluation.lexicon.LexiconTrie.tensors / .num_fold) - and item_segment int32 [B] on x's device ->
+    (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k], words int32 [B,k][, path rows [B,max_len,C]]): the k most
+    likely lexicon words of each item's segment, best first.  No host synchronisation; limits are checked by the library."""
+    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj")
+    if xproj.shape != x.shape or xproj.device != x.device:
+        raise GlassLibraryError(f"beam_search_lexicon: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
+    B, T, D = x.shape
+    k, C, L = int(beam_width), int(num_classes), int(max_len)
+    dev = x.device
+    F = int(trie["F"])
+    MW = (F + 31) // 32
+    arrays = {n: trie.get(n) for n in ("child_mask", "child_base", "node_word", "seg_root", "fold")}
+    N = S = 0
+    for n, t in arrays.items():
+        if t is None:
+            continue
+        _i32(t, n)
+        if t.device != dev:
+            raise GlassLibraryError(f"beam_search_lexicon: {n} on {t.device}, x on {dev}")
+    if arrays["child_mask"] is not None:
+        cm = arrays["child_mask"]
+        N = int(cm.shape[0])
+        if cm.dim() != 2 or (1 <= F <= 256 and cm.shape[1] != MW):      # (an F outside 1..256 is the library's to refuse)
+            raise GlassLibraryError(f"beam_search_lexicon: child_mask {tuple(cm.shape)} is not [N, MW={MW}] (F={F})")
+        for n in ("child_base", "node_word"):
+            if arrays[n] is not None and tuple(arrays[n].shape) != (N,):
+                raise GlassLibraryError(f"beam_search_lexicon: {n} {tuple(arrays[n].shape)} is not [N={N}]")
+    if arrays["seg_root"] is not None:
+        S = int(arrays["seg_root"].numel())
+    if arrays["fold"] is not None and tuple(arrays["fold"].shape) != (C,):
+        raise GlassLibraryError(f"beam_search_lexicon: fold {tuple(arrays['fold'].shape)} is not [C={C}]")
+    _i32(item_segment, "item_segment")
+    if tuple(item_segment.shape) != (B,) or item_segment.device != dev:
+        raise GlassLibraryError(f"beam_search_lexicon: item_segment {tuple(item_segment.shape)} on {item_segment.device} is not [B={B}] on {dev}")
+    symbols = torch.empty((B, max(k, 0), max(L, 0)), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
+    lengths = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    words = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
+    path = torch.empty((B, max(L, 0), max(C, 0)), dtype=torch.float32, device=dev) if path_probs else None
+    w = _decoder_weights(weights)
+    nbytes = int(lib().glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, L))
+    ws = _workspace(nbytes, dev)
+    check(lib().glass_beam_search_lexicon(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos),
+                                          _opt(arrays["child_mask"]), _opt(arrays["child_base"]), _opt(arrays["node_word"]),
+                                          _opt(arrays["seg_root"]), _opt(arrays["fold"]), N, S, F, _opt(item_segment),
+                                          _dev(symbols), _dev(scores), _dev(lengths), _dev(words), _opt(path), _dev(ws), nbytes,
+                                          stream_handle()), "glass_beam_search_lexicon")
+    return (symbols, scores, lengths, words, path) if path_probs else (symbols, scores, lengths, words)
+
+
 def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: torch.Tensor, lengths: Optional[torch.Tensor],
                   num_classes: int, max_len: int, eos: int, probs: bool = False, logits: bool = False):
     """the decoder with the emitted symbols given (glass_forced_decode; reference AttentionRecognitionHead.forward): x, xproj
