@@ -1,6 +1,7 @@
-// Shared device helpers of the proposal kernels (proposals.hip, rpn.hip).
+// Shared device helpers of the proposal kernels (proposals.hip, rpn.hip, view_merge.hip).
 #pragma once
 #include "common.h"
+#include "rotated_iou.h"
 
 typedef unsigned long long u64;
 typedef unsigned int u32;
@@ -42,3 +43,47 @@ __device__ __forceinline__ float floor_mod(float a, float b) {  // torch.remaind
   return m;
 }
 
+// ------------------------------------------------------------------ pieces of the blocked greedy NMS (proposals.hip nms_select_kernel,
+// view_merge.hip merge_views_kernel): one workgroup of NMS_THREADS, chunks of 64 sorted candidates
+constexpr int NMS_SMAX = 8192;
+constexpr int NMS_KEEP_MAX = 1024;
+constexpr int NMS_THREADS = 1024;
+
+// the early exit of rotated_iou (rotated_iou.h: circumscribed circles disjoint -> IoU exactly 0), as a predicate of its own
+__device__ __forceinline__ bool rbox_far_apart(const RBox& a, const RBox& b) {
+#pragma clang fp contract(off)
+  const float dx = a.cx - b.cx, dy = a.cy - b.cy;
+  const float rr = 0.5f * (sqrtf(a.w * a.w + a.h * a.h) + sqrtf(b.w * b.w + b.h * b.h));
+  return dx * dx + dy * dy > rr * rr * 1.001f + 1e-2f;
+}
+
+// `total` box pairs, pair pr -> (i, j) by `decode`; the pairs that are not far apart - the ones that run the polygon clipping,
+// whose point lists live in scratch - are collected per wavefront (ballot compaction, 128 entries each) and evaluated 64 at a
+// time with every lane busy, instead of by whichever lanes of a round happen to hold one (postprocess.hip: pp_for_pairs).
+template <class Decode, class Far, class Heavy>
+__device__ __forceinline__ void nms_for_pairs(int total, unsigned short* queue, Decode decode, Far far, Heavy heavy) {
+  const int lane = threadIdx.x & 63;
+  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+  int qn = 0;                                                       // (wavefront-uniform)
+  for (int base = threadIdx.x & ~63; base < total; base += NMS_THREADS) {
+    const int pr = base + lane;
+    int i = 0, j = 0;
+    bool near = false;
+    if (pr < total) {
+      decode(pr, i, j);
+      near = !far(i, j);
+    }
+    const unsigned long long m = __ballot(near);
+    if (near) queue[qn + __popcll(m & below)] = (unsigned short)((i << 6) | j);
+    qn += __popcll(m);
+    if (qn >= 64) {
+      qn -= 64;
+      const int e = queue[qn + lane];
+      heavy(e >> 6, e & 63);
+    }
+  }
+  if (lane < qn) {
+    const int e = queue[lane];
+    heavy(e >> 6, e & 63);
+  }
+}

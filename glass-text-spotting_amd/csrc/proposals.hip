@@ -33,10 +33,6 @@ extern "C" int glass_pairwise_iou_rotated(const float* boxes1, int n1, const flo
 }
 
 // ------------------------------------------------------------------ filter + sort + greedy NMS
-constexpr int NMS_SMAX = 8192;
-constexpr int NMS_KEEP_MAX = 1024;
-constexpr int NMS_THREADS = 1024;
-
 struct NmsParams {
   const float* boxes; const float* scores; const int* cat; const int* valid_count; const int* image_hw;
   int N, S;
@@ -44,45 +40,6 @@ struct NmsParams {
   int post_topk, flags;
   float* out_boxes; float* out_scores; int* out_index; int* out_count;
 };
-
-// the early exit of rotated_iou (rotated_iou.h: circumscribed circles disjoint -> IoU exactly 0), as a predicate of its own
-__device__ __forceinline__ bool rbox_far_apart(const RBox& a, const RBox& b) {
-#pragma clang fp contract(off)
-  const float dx = a.cx - b.cx, dy = a.cy - b.cy;
-  const float rr = 0.5f * (sqrtf(a.w * a.w + a.h * a.h) + sqrtf(b.w * b.w + b.h * b.h));
-  return dx * dx + dy * dy > rr * rr * 1.001f + 1e-2f;
-}
-
-// `total` box pairs, pair pr -> (i, j) by `decode`; the pairs that are not far apart - the ones that run the polygon clipping,
-// whose point lists live in scratch - are collected per wavefront (ballot compaction, 128 entries each) and evaluated 64 at a
-// time with every lane busy, instead of by whichever lanes of a round happen to hold one (postprocess.hip: pp_for_pairs).
-template <class Decode, class Far, class Heavy>
-__device__ __forceinline__ void nms_for_pairs(int total, unsigned short* queue, Decode decode, Far far, Heavy heavy) {
-  const int lane = threadIdx.x & 63;
-  const unsigned long long below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-  int qn = 0;                                                       // (wavefront-uniform)
-  for (int base = threadIdx.x & ~63; base < total; base += NMS_THREADS) {
-    const int pr = base + lane;
-    int i = 0, j = 0;
-    bool near = false;
-    if (pr < total) {
-      decode(pr, i, j);
-      near = !far(i, j);
-    }
-    const unsigned long long m = __ballot(near);
-    if (near) queue[qn + __popcll(m & below)] = (unsigned short)((i << 6) | j);
-    qn += __popcll(m);
-    if (qn >= 64) {
-      qn -= 64;
-      const int e = queue[qn + lane];
-      heavy(e >> 6, e & 63);
-    }
-  }
-  if (lane < qn) {
-    const int e = queue[lane];
-    heavy(e >> 6, e & 63);
-  }
-}
 
 __global__ __launch_bounds__(NMS_THREADS) void nms_select_kernel(NmsParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char dyn_smem[];

@@ -1,5 +1,7 @@
 """`GlassRunner`: the single-image predictor the reference ships, on the HIP pipeline.
 
+`run_tiled` is the large-image form: overlapping tiles at full resolution as one batch, merged on the device.
+
 Mirrors reference glass/inference/glass_runner.py:20-153: cfg set-up (:31-39), model build and
 checkpoint load (:52-60), channel handling (:83-87), on-device bilinear resize policy
 (`get_inference_scale_ratio` :111-121, `_image_to_tensor` :123-148), model call (:93-96),
@@ -19,8 +21,9 @@ from ..modeling.meta_arch.glass_rcnn import build_model
 from ..modeling.recognition.text_encoder import TextEncoder
 from ..ops import native as K
 from ..postprocess import build_post_processor
-from ..structures.core import Instances
+from ..structures.core import Instances, RotatedBoxes
 from ..utils.host import limit_host_threads
+from .tiling import plan_tiles
 
 
 class GlassRunner:
@@ -57,20 +60,23 @@ class GlassRunner:
     def _image_to_tensor(self, original_image: np.ndarray):
         """uint8 HWC on host -> float CHW on device, resized by the reference policy; one H2D copy
         of the uint8 image and one fused convert+resize kernel."""
+        scale_ratio = self.get_inference_scale_ratio(original_image.shape)
+        return self._image_at_scale(original_image, scale_ratio), scale_ratio
+
+    def _image_at_scale(self, original_image: np.ndarray, scale_ratio):
+        """the device image `_image_to_tensor` makes, at a ratio of the caller's choice"""
         if self.input_format == "GREY":
             # reference glass/utils/common_utils.py:29-43 (rgb2grey, three_channels=True), on the host uint8 image as
             # the reference does: Y'709 weights on channels 0,1,2, truncated to uint8, replicated three times
             g = np.uint8(0.2125 * original_image[:, :, 0] + 0.7154 * original_image[:, :, 1] + 0.0721 * original_image[:, :, 2])
             original_image = np.repeat(g[:, :, None], 3, axis=2)
         height, width = original_image.shape[:2]
-        scale_ratio = self.get_inference_scale_ratio(original_image.shape)
         if scale_ratio != 1:
             nh, nw = int(np.round(scale_ratio * height)), int(np.round(scale_ratio * width))
         else:
             nh, nw = height, width
         u8 = torch.from_numpy(np.ascontiguousarray(original_image)).to(self.device)
-        chw = K.image_u8hwc_to_chw(u8, (nh, nw), flip_channels=(self.input_format == "RGB"))
-        return chw, scale_ratio
+        return K.image_u8hwc_to_chw(u8, (nh, nw), flip_channels=(self.input_format == "RGB"))
 
     def run_batch(self, images: Sequence[np.ndarray]) -> List[Instances]:
         """Many images per step with per-image results identical to image-by-image calls.  detectron2
@@ -116,6 +122,116 @@ class GlassRunner:
         for r in out:
             self.logger.info(f"Post-processing output is {len(r)} word instances")
         return out
+
+    def run_tiled(self, image: np.ndarray, tile: int = 1024, overlap: int = 256, border: int = 16, scale: float = 1.0,
+                  full_view: bool = True, nms_thresh: Optional[float] = None, batch_size: int = 8) -> Instances:
+        """One large image at (`scale` times) its own resolution: `__call__` shrinks an image whose long side exceeds
+        INPUT.MAX_SIZE_TEST, and the small words of a scan or a receipt are gone before the RPN sees them.  Here the image is cut
+        into overlapping tiles (tiling.plan_tiles) that run through the model as batches of at most `batch_size`; with
+        `full_view`, the input `__call__` would feed runs as one more view, for the words too large to lie whole in a tile.
+        ops.native.merge_views (glass_merge_views) makes ONE detection set of them on the device: a tile's word counts if its
+        corners keep `border` pixels from the tile's interior edges and (with the full view) its extent is at most
+        L = overlap - 2*border, a word of the full view if its extent is above L, and of the copies of a word that several views
+        hold the best-scored one stays (rotated IoU >= `nms_thresh`, default MODEL.ROI_HEADS.NMS_THRESH_TEST, between boxes of
+        different views).  The merged set - at most 1024 detections - then takes the ordinary way through the word
+        post-processor, with the boxes in the original image's pixels."""
+        heads = self.model.roi_heads
+        if getattr(heads, "mask_inference", False):
+            raise NotImplementedError("run_tiled: MODEL.ROI_MASK_HEAD.MASK_INFERENCE is on; masks are pasted per tile frame and "
+                                      "merging them is not supported")
+        if getattr(getattr(heads, "recognizer_head", None), "image_segments", None) is not None:
+            raise NotImplementedError("run_tiled: the recogniser head carries per-image lexicon segments (image_segments); the "
+                                      "views of a tiled image are not images of that list - set the lexicon with one segment")
+        height, width = image.shape[:2]
+        scale = float(scale)
+        if not (scale > 0 and np.isfinite(scale)):
+            raise ValueError(f"run_tiled: scale={scale}")
+        work = self._image_at_scale(image, scale if scale != 1.0 else 1)
+        plan = plan_tiles(work.shape[1], work.shape[2], tile, overlap, border)
+        L = float(plan.max_whole)
+        inf = float("inf")
+        with_full = bool(full_view) and len(plan.tiles) > 1
+        Kdet = int(self.cfg.TEST.DETECTIONS_PER_IMAGE)
+        V = len(plan.tiles) + int(with_full)
+        if V * Kdet > K.MERGE_VIEWS_MAX_SLOTS or V > K.MERGE_VIEWS_MAX_VIEWS:
+            fit = tile
+            while fit < (1 << 20):
+                fit += 32
+                p = plan_tiles(work.shape[1], work.shape[2], fit, overlap, border)
+                n = len(p.tiles) + int(bool(full_view) and len(p.tiles) > 1)
+                if n * Kdet <= K.MERGE_VIEWS_MAX_SLOTS and n <= K.MERGE_VIEWS_MAX_VIEWS:
+                    break
+            raise ValueError(f"run_tiled: {V} views of {Kdet} detections each exceed the {K.MERGE_VIEWS_MAX_SLOTS} slots (and "
+                             f"{K.MERGE_VIEWS_MAX_VIEWS} views) of one merge; tile={fit} fits this image")
+        # ---- the views: (input, frame transform, keep rectangle, size band)
+        inputs, xform, keep, band = [], [], [], []
+        for t in plan.tiles:
+            crop = work[:, t.y0:t.y0 + t.h, t.x0:t.x0 + t.w]
+            inputs.append({"image": crop, "height": t.h, "width": t.w})
+            xform.append([float(t.x0), float(t.y0), 1.0])
+            keep.append(list(t.keep))
+            band.append([-inf, L if with_full else inf])       # (one tile has no full view beside it: it keeps every size)
+        calls = [inputs[i:i + max(int(batch_size), 1)] for i in range(0, len(inputs), max(int(batch_size), 1))]
+        if with_full:
+            full, rho = self._image_to_tensor(image)
+            calls.append([{"image": full, "height": full.shape[1], "width": full.shape[2]}])
+            xform.append([0.0, 0.0, scale / rho])
+            keep.append([-inf, -inf, inf, inf])
+            band.append([L, inf])
+        # ---- the model, call by call; the padded device batches joined along the view axis
+        dets = []
+        for call in calls:
+            det = getattr(self.model(call), "batch", None)
+            if det is None:
+                raise RuntimeError("run_tiled needs the model's padded device batch (POST_PROCESSING.INFLATE_RATIO / DROP_OVERLAPPING "
+                                   "take the list-wise path, which has none)")
+            if tuple(det.scores.shape) != (len(call), Kdet):
+                raise RuntimeError(f"run_tiled: a batch of scores {tuple(det.scores.shape)}, expected {(len(call), Kdet)}")
+            dets.append(det)
+        dev = self.device
+
+        def joined(name, tail):
+            parts = [getattr(d, name, None) for d in dets]
+            if all(p is None for p in parts):
+                return None
+            return torch.cat([p if p is not None else torch.zeros((d.scores.shape[0], Kdet) + tail, dtype=torch.float32, device=dev)
+                              for p, d in zip(parts, dets)], 0)
+        T = self.cfg.MODEL.ROI_RECOGNIZER_HEAD.MAX_WORD_LENGTH + 1
+        C = len(self.cfg.MODEL.ROI_RECOGNIZER_HEAD.CHARACTER_SET) + 2
+        boxes, scores = joined("boxes", (5,)), joined("scores", ())
+        orient, text, text_dist = joined("orient", (2,)), joined("text", (T, C)), joined("text_dist", (T, C))
+        counts = torch.cat([d.counts_dev for d in dets], 0)
+        if text is None and sum(sum(d.counts_host) for d in dets) > 0:
+            raise RuntimeError("recognizer output missing")
+        # ---- the merge, and the survivors' rows gathered by their source slot
+        thr = float(nms_thresh or self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST)
+        m = K.merge_views(boxes.contiguous(), scores.contiguous(), counts.contiguous(), K.upload(xform, torch.float32, dev),
+                          K.upload(keep, torch.float32, dev), K.upload(band, torch.float32, dev), thr, K.MERGE_VIEWS_MAX_OUT)
+        src = m["src"].long()
+        gather = lambda t: None if t is None else t.reshape((V * Kdet,) + tuple(t.shape[2:])).index_select(0, src).unsqueeze(0)
+        orient, text, text_dist = gather(orient), gather(text), gather(text_dist)
+        n_out, truncated = m["count"].tolist()                      # the one read of out_count
+        if truncated:
+            self.logger.warning(f"run_tiled: more than {K.MERGE_VIEWS_MAX_OUT} merged detections; the lowest-scored are cut off")
+        if self.post_process_flag:
+            if text is None:          # no detections in any view
+                text = torch.zeros((1, K.MERGE_VIEWS_MAX_OUT, T, C), dtype=torch.float32, device=dev)
+            sc = torch.tensor([[1.0 / scale, 1.0 / scale]], dtype=torch.float32).to(dev)
+            res = self.post_processor.process_padded(m["boxes"].unsqueeze(0), m["scores"].unsqueeze(0), m["count"][:1], text, sc,
+                                                     [(height, width)], {"orientations": orient, "pred_text_dist": text_dist})[0]
+        else:
+            res = Instances((height, width))
+            res.pred_boxes = RotatedBoxes(m["boxes"][:n_out])
+            res.scores = m["scores"][:n_out]
+            res.pred_classes = torch.zeros((n_out,), dtype=torch.int64, device=dev)
+            for name, t in (("orientations", orient), ("pred_text_prob", text), ("pred_text_dist", text_dist)):
+                if t is not None:
+                    res.set(name, t[0, :n_out])
+            if scale != 1:
+                res.pred_boxes.scale(1 / scale, 1 / scale)
+        self.logger.info(f"Tiled inference: {len(plan.tiles)} tiles{' + the full view' if with_full else ''}, {n_out} merged "
+                         f"detections, {len(res)} word instances")
+        return res
 
     def __call__(self, original_image: np.ndarray) -> Instances:
         return self.run_batch([original_image])[0]

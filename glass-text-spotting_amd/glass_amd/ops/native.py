@@ -1576,7 +1576,55 @@ def postprocess_words(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.T
     return out
 
 
-LEXICON_MAX_QUERY = 64        # symbols of one query: the bit-parallel pattern is one 64-bit word
+MERGE_VIEWS_MAX_VIEWS = 256      # csrc/view_merge.hip MV_VMAX
+MERGE_VIEWS_MAX_SLOTS = 8192     # V * K of one merge: NMS_SMAX, the limit of glass_rotated_nms_select
+MERGE_VIEWS_MAX_OUT = 1024       # NMS_KEEP_MAX = POSTPROCESS_MAX_K: what the word post-processor takes per image
+
+
+def merge_views(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.Tensor, view_xform: torch.Tensor,
+                keep_rect: torch.Tensor, size_range: torch.Tensor, nms_thresh: float, max_out: int = MERGE_VIEWS_MAX_OUT) -> dict:
+    """The padded detections of V views of ONE image -> one detection set in the image's frame (glass_merge_views,
+    include/glass_hip_ext_views.h has the contract): boxes [V,K,5] in each view's pixels, scores [V,K], counts int32 [V],
+    view_xform [V,3] (ox, oy, inv), keep_rect [V,4] (kx0, ky0, kx1, ky1, may be +-inf), size_range [V,2] (lo, hi), all on
+    the device.  Returns {"boxes" [max_out,5], "scores" [max_out], "src" int32 [max_out] = v*K + s, "count" int32 [2] =
+    (rows, truncated)} as views of one zeroed buffer.  Stream-ordered, no read-back; a wrong shape, dtype, device or limit is
+    a ValueError before any launch."""
+    named = (("boxes", boxes, torch.float32), ("scores", scores, torch.float32), ("counts", counts, torch.int32),
+             ("view_xform", view_xform, torch.float32), ("keep_rect", keep_rect, torch.float32),
+             ("size_range", size_range, torch.float32))
+    for name, t, dt in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"merge_views: {name} must be a contiguous {dt} tensor on the device (got "
+                             f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', None)})")
+        if t.device != boxes.device:
+            raise ValueError(f"merge_views: {name} is on {t.device}, boxes on {boxes.device}")
+    if boxes.dim() != 3 or boxes.shape[2] != 5:
+        raise ValueError(f"merge_views: boxes {tuple(boxes.shape)}: needs [V, K, 5]")
+    V, K = int(boxes.shape[0]), int(boxes.shape[1])
+    for name, t, shape in (("scores", scores, (V, K)), ("counts", counts, (V,)), ("view_xform", view_xform, (V, 3)),
+                           ("keep_rect", keep_rect, (V, 4)), ("size_range", size_range, (V, 2))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"merge_views: {name} {tuple(t.shape)}: needs {shape}")
+    if V > MERGE_VIEWS_MAX_VIEWS or not 1 <= K <= MERGE_VIEWS_MAX_OUT or V * K > MERGE_VIEWS_MAX_SLOTS:
+        raise ValueError(f"merge_views: V={V} views of K={K} slots: needs V <= {MERGE_VIEWS_MAX_VIEWS}, 1 <= K <= "
+                         f"{MERGE_VIEWS_MAX_OUT} and V * K <= {MERGE_VIEWS_MAX_SLOTS}")
+    max_out, nms_thresh = int(max_out), float(nms_thresh)
+    if not 1 <= max_out <= MERGE_VIEWS_MAX_OUT:
+        raise ValueError(f"merge_views: max_out={max_out} (1..{MERGE_VIEWS_MAX_OUT})")
+    if not math.isfinite(nms_thresh):
+        raise ValueError(f"merge_views: nms_thresh={nms_thresh} is not finite")
+    dev = boxes.device
+    ob, os_, src, cnt = zeros_views([((max_out, 5), torch.float32), ((max_out,), torch.float32), ((max_out,), torch.int32),
+                                     ((2,), torch.int32)], dev)
+    ws_bytes = int(lib().glass_merge_views_workspace_bytes(V, K))
+    ws = _workspace(ws_bytes, dev)                   # needs no initialisation
+    check(lib().glass_merge_views(_dev(boxes), _dev(scores), _dev(counts), _dev(view_xform), _dev(keep_rect), _dev(size_range),
+                                  V, K, nms_thresh, max_out, _dev(ob), _dev(os_), _dev(src), _dev(cnt), _dev(ws), ws_bytes,
+                                  stream_handle()), "glass_merge_views")
+    return {"boxes": ob, "scores": os_, "src": src, "count": cnt}
+
+
+LEXICON_MAX_QUERY = 64       # symbols of one query: the bit-parallel pattern is one 64-bit word
 
 
 def _lexicon_queries(queries: Sequence[bytes]):
