@@ -21,8 +21,17 @@
 // Every loop is bounded by a size read once: a parent chain strictly decreases, a union lowers one of its two ends every
 // turn, the walk is cut at the number of directed boundary edges of the window (status 3 if that ever happens).  No wait
 // on another workgroup.
+//
+// RoI form (glass_roi_mask_windows / glass_roi_mask_rings_count, include/glass_hip_feature_roimask.h): the pasted [R][H][W]
+// tensor never exists.  Whether a pixel is set is the paste's own arithmetic (paste_value of mask_paste_common.h) >= the
+// threshold, evaluated from the M x M RoI mask and its box in the two stages that read pixels: the window stage, over the
+// box's candidate rectangle (paste_rect: clipped to the image before it is an integer) instead of the whole image, and the
+// first labelling stage.  The windows are the same tight ones, so the workspace, the labels, the winners and the rings are
+// those of the byte form on the pasted tensor, bit for bit; every later stage is shared.
 #include <climits>
 #include "common.h"
+#include "glass_hip_feature_roimask.h"
+#include "mask_paste_common.h"
 
 namespace {
 
@@ -62,6 +71,43 @@ __device__ __forceinline__ void mr_note(long idx, int W, int& xlo, int& ylo, int
   xhi = max(xhi, x);
   ylo = min(ylo, y);
   yhi = max(yhi, y);
+}
+
+// the workgroup's extremes of one mask -> its window (integer atomicMin / atomicMax); called by every thread, once per mask.
+// For the RoI form's window stage: the reduction mr_window_kernel ends with, which stays written out there so that the
+// byte form's code is what it was (called from there, force-inlined, this helper compiles to 3370 instructions for that
+// kernel instead of 3366, whether it takes the LDS array by pointer or by reference).
+__device__ __forceinline__ void mr_window_reduce(int xlo, int ylo, int xhi, int yhi, int (&red)[MR_WAVES][4], int* __restrict__ win, int r) {
+  const int tid = threadIdx.x;
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) {
+    xlo = min(xlo, __shfl_xor(xlo, off));
+    ylo = min(ylo, __shfl_xor(ylo, off));
+    xhi = max(xhi, __shfl_xor(xhi, off));
+    yhi = max(yhi, __shfl_xor(yhi, off));
+  }
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = xlo;
+    red[tid >> 6][1] = ylo;
+    red[tid >> 6][2] = xhi;
+    red[tid >> 6][3] = yhi;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int k = 1; k < MR_WAVES; ++k) {
+      xlo = min(xlo, red[k][0]);
+      ylo = min(ylo, red[k][1]);
+      xhi = max(xhi, red[k][2]);
+      yhi = max(yhi, red[k][3]);
+    }
+    if (xhi >= 0) {
+      atomicMin(&win[4 * r + 0], xlo);
+      atomicMin(&win[4 * r + 1], ylo);
+      atomicMax(&win[4 * r + 2], xhi);
+      atomicMax(&win[4 * r + 3], yhi);
+    }
+  }
+  __syncthreads();
 }
 
 // grid (chunks of a mask, masks); a mask is a flat run of H * W bytes: the bytes before the first 16-byte boundary and
@@ -128,6 +174,41 @@ __global__ __launch_bounds__(MR_THREADS) void mr_window_kernel(const unsigned ch
     }
     __syncthreads();
   }
+}
+
+// RoI form of the window stage, grid (workgroups over a rectangle, masks): the set pixels are looked for in the box's
+// candidate rectangle only.  The loop runs over the clipped rectangle's pixel count, read once.
+__global__ __launch_bounds__(MR_THREADS) void mr_roi_window_kernel(const float* __restrict__ masks, const float* __restrict__ boxes,
+                                                                   int R, int M, int H, int W, float threshold,
+                                                                   int* __restrict__ win) {
+  const int tid = threadIdx.x;
+  __shared__ int red[MR_WAVES][4];
+  for (int r = blockIdx.y; r < R; r += gridDim.y) {                    // uniform over the workgroup
+    const int4 rc = paste_rect(boxes + (size_t)r * 5, M, H, W);
+    if (rc.z < rc.x) continue;                                         // nothing can be set: the window stays empty
+    const int rw = rc.z - rc.x + 1, rh = rc.w - rc.y + 1;
+    const long long npx = (long long)rw * rh;
+    const PasteFrame f = paste_frame(boxes + (size_t)r * 5, M);
+    const float* mk = masks + (size_t)r * M * M;
+    int xlo = INT_MAX, ylo = INT_MAX, xhi = -1, yhi = -1;
+    for (long long i = (long long)blockIdx.x * MR_THREADS + tid; i < npx; i += (long long)gridDim.x * MR_THREADS) {
+      const int y = (int)(i / rw), x = (int)(i - (long long)y * rw);
+      const int px = rc.x + x, py = rc.y + y;
+      if (paste_value(f, mk, M, px, py) >= threshold) {
+        xlo = min(xlo, px);
+        xhi = max(xhi, px);
+        ylo = min(ylo, py);
+        yhi = max(yhi, py);
+      }
+    }
+    mr_window_reduce(xlo, ylo, xhi, yhi, red, win, r);
+  }
+}
+
+// the candidate rectangles themselves, for whoever wants to see what the window stage looked at
+__global__ void mr_roi_rect_kernel(const float* __restrict__ boxes, int R, int M, int H, int W, int4* __restrict__ rects) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r < R) rects[r] = paste_rect(boxes + (size_t)r * 5, M, H, W);
 }
 
 // one workgroup: out[0] = 0, out[k + 1] = out[k] + value(k), *total = out[n]; every thread sums a contiguous slice and the
@@ -206,6 +287,17 @@ __device__ __forceinline__ void mr_union(int* L, int a, int b, long long bound) 
 
 enum { MR_INIT = 0, MR_MERGE = 1, MR_COUNT = 2, MR_SELECT = 3 };
 
+// MR_INIT for the 64 pixels of one wavefront, whatever told it which are set: a set pixel starts as the first pixel of its run
+__device__ __forceinline__ void mr_init_labels(bool in, bool set, int lane, unsigned long long below, int p, int* L, int* C) {
+  const unsigned long long bal = __ballot(set);
+  const unsigned long long gaps = ~bal & below;                 // unset lanes below this one
+  const int start = gaps ? 64 - __clzll((long long)gaps) : 0;   // first lane of this lane's run
+  if (in) {
+    L[p] = set ? p - (lane - start) : -1;
+    C[p] = 0;
+  }
+}
+
 // grid (wavefront groups, masks): wavefront `it` of a mask owns the 64 pixels (y, xs .. xs + 63) of its window
 template <int STAGE>
 __global__ __launch_bounds__(MR_THREADS) void mr_label_kernel(const unsigned char* __restrict__ masks, int R, int H, int W,
@@ -223,7 +315,7 @@ __global__ __launch_bounds__(MR_THREADS) void mr_label_kernel(const unsigned cha
     const long long npix = (long long)q.w * q.h;
     int* L = labels + pix_off[r];
     int* C = cnt + pix_off[r];
-    const unsigned char* m = masks + (size_t)r * H * W + (size_t)q.y0 * W + q.x0;
+    const unsigned char* m = STAGE == MR_INIT ? masks + (size_t)r * H * W + (size_t)q.y0 * W + q.x0 : nullptr;   // read by MR_INIT only
     for (long long it = (long long)blockIdx.x * MR_WAVES + wid; it < items; it += (long long)gridDim.x * MR_WAVES) {
       const int y = (int)(it / segs);
       const int xs = (int)(it - (long long)y * segs) * 64;
@@ -231,14 +323,7 @@ __global__ __launch_bounds__(MR_THREADS) void mr_label_kernel(const unsigned cha
       const bool in = x < q.w;
       const int p = y * q.w + x;
       if (STAGE == MR_INIT) {
-        const bool set = in && m[(size_t)y * W + x] != 0;
-        const unsigned long long bal = __ballot(set);
-        const unsigned long long gaps = ~bal & below;                 // unset lanes below this one
-        const int start = gaps ? 64 - __clzll((long long)gaps) : 0;   // first lane of this lane's run
-        if (in) {
-          L[p] = set ? p - (lane - start) : -1;
-          C[p] = 0;
-        }
+        mr_init_labels(in, in && m[(size_t)y * W + x] != 0, lane, below, p, L, C);
       } else if (STAGE == MR_MERGE) {
         const bool set = in && mr_load(L + p) >= 0;                    // the sign of a label never changes after MR_INIT
         const unsigned long long bal = __ballot(set);
@@ -273,6 +358,36 @@ __global__ __launch_bounds__(MR_THREADS) void mr_label_kernel(const unsigned cha
         }
         if (lane == 0 && key) atomicMax(best + r, key);
       }
+    }
+  }
+}
+
+// MR_INIT of the RoI form, same grid and the same walk over the window as mr_label_kernel: a pixel is set iff the paste's
+// value there reaches the threshold.  The window lies inside the image (window_of), the mask taps inside [M][M] (paste_value).
+__global__ __launch_bounds__(MR_THREADS) void mr_roi_label_init_kernel(const float* __restrict__ masks, const float* __restrict__ boxes,
+                                                                       int R, int M, int H, int W, float threshold,
+                                                                       const int* __restrict__ win,
+                                                                       const long long* __restrict__ pix_off, int* labels, int* cnt,
+                                                                       const int* __restrict__ status) {
+  if (*status != MR_OK) return;
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+  for (int r = blockIdx.y; r < R; r += gridDim.y) {
+    const Window q = window_of(win + 4 * r, H, W);
+    if (q.w == 0) continue;
+    const int segs = (q.w + 63) / 64;
+    const long long items = (long long)q.h * segs;
+    int* L = labels + pix_off[r];
+    int* C = cnt + pix_off[r];
+    const PasteFrame f = paste_frame(boxes + (size_t)r * 5, M);
+    const float* mk = masks + (size_t)r * M * M;
+    for (long long it = (long long)blockIdx.x * MR_WAVES + wid; it < items; it += (long long)gridDim.x * MR_WAVES) {
+      const int y = (int)(it / segs);
+      const int xs = (int)(it - (long long)y * segs) * 64;
+      const int x = xs + lane;
+      const bool in = x < q.w;
+      const bool set = in && paste_value(f, mk, M, q.x0 + x, q.y0 + y) >= threshold;
+      mr_init_labels(in, set, lane, below, y * q.w + x, L, C);
     }
   }
 }
@@ -406,6 +521,49 @@ bool sizes_ok(int R, int H, int W) { return R >= 0 && H >= 1 && H <= 65535 && W 
 
 unsigned grid_masks(int R) { return (unsigned)(R < 65535 ? R : 65535); }
 
+// GLASS_CHECK_LAUNCH with the entry point's name and the stage in the message
+#define MR_CHECK_LAUNCH(what, stage)                                                          \
+  do {                                                                                        \
+    hipError_t e__ = hipGetLastError();                                                       \
+    if (e__ != hipSuccess) {                                                                  \
+      glass_set_error("%s (%s): launch failed: %s", what, stage, hipGetErrorString(e__));     \
+      return GLASS_EHIP;                                                                      \
+    }                                                                                         \
+  } while (0)
+
+// the count after the form's own argument checks: offsets, the four labelling stages (`init` enqueues the first, the only
+// one that looks at pixels), the counting walk and the ring offsets
+template <typename Init>
+int rings_count(const char* what, int R, int H, int W, const int* windows, void* workspace, int64_t workspace_bytes, int* ring_off,
+                int* status, hipStream_t st, Init init) {
+  GLASS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "%s: workspace must be 16-byte aligned", what);
+  const Layout l = layout_of(R);
+  GLASS_CHECK_ARG(workspace_bytes >= l.labels, "%s: workspace of %lld bytes, needs %lld and the windows", what,
+                  (long long)workspace_bytes, (long long)l.labels);
+  const long long cap_px = cap_px_of(workspace_bytes, l);
+  char* ws = static_cast<char*>(workspace);
+  long long* pix_off = reinterpret_cast<long long*>(ws);
+  unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + l.best);
+  int* nvert = reinterpret_cast<int*>(ws + l.nvert);
+  int* labels = reinterpret_cast<int*>(ws + l.labels);
+  int* cnt = labels + cap_px;
+  const unsigned char* none = nullptr;                                 // the later stages read labels only
+  hipLaunchKernelGGL(mr_offsets_kernel, dim3(1), dim3(MR_THREADS), 0, st, windows, R, H, W, cap_px, pix_off, best, nvert, status);
+  MR_CHECK_LAUNCH(what, "offsets");
+  const dim3 g(MR_LABEL_GRID_X, grid_masks(R));
+  init(g, st, pix_off, labels, cnt, best);
+  hipLaunchKernelGGL(mr_label_kernel<MR_MERGE>, g, dim3(MR_THREADS), 0, st, none, R, H, W, windows, pix_off, labels, cnt, best, status);
+  hipLaunchKernelGGL(mr_label_kernel<MR_COUNT>, g, dim3(MR_THREADS), 0, st, none, R, H, W, windows, pix_off, labels, cnt, best, status);
+  hipLaunchKernelGGL(mr_label_kernel<MR_SELECT>, g, dim3(MR_THREADS), 0, st, none, R, H, W, windows, pix_off, labels, cnt, best, status);
+  MR_CHECK_LAUNCH(what, "label");
+  hipLaunchKernelGGL(mr_trace_kernel<false>, dim3(grid_masks(R)), dim3(MR_THREADS), 0, st, R, H, W, windows, pix_off, cap_px, labels, best,
+                     nvert, (const int*)nullptr, (int2*)nullptr, 0ll, status);
+  MR_CHECK_LAUNCH(what, "trace");
+  hipLaunchKernelGGL(mr_ring_offsets_kernel, dim3(1), dim3(MR_THREADS), 0, st, nvert, R, ring_off, status);
+  MR_CHECK_LAUNCH(what, "ring offsets");
+  return GLASS_OK;
+}
+
 }  // namespace
 
 extern "C" int glass_mask_windows(const uint8_t* masks, int R, int H, int W, int* windows, glass_stream_t stream) {
@@ -438,32 +596,11 @@ extern "C" int glass_mask_rings_count(const uint8_t* masks, int R, int H, int W,
   GLASS_CHECK_ARG(sizes_ok(R, H, W), "glass_mask_rings_count: bad sizes R=%d H=%d W=%d (H, W in 1..65535, H * W < 2^31)", R, H, W);
   if (R == 0) return GLASS_OK;
   GLASS_CHECK_ARG(masks && windows && workspace && ring_off && status, "glass_mask_rings_count: null pointer");
-  GLASS_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "glass_mask_rings_count: workspace must be 16-byte aligned");
-  const Layout l = layout_of(R);
-  GLASS_CHECK_ARG(workspace_bytes >= l.labels, "glass_mask_rings_count: workspace of %lld bytes, needs %lld and the windows",
-                  (long long)workspace_bytes, (long long)l.labels);
-  const long long cap_px = cap_px_of(workspace_bytes, l);
-  char* ws = static_cast<char*>(workspace);
-  long long* pix_off = reinterpret_cast<long long*>(ws);
-  unsigned long long* best = reinterpret_cast<unsigned long long*>(ws + l.best);
-  int* nvert = reinterpret_cast<int*>(ws + l.nvert);
-  int* labels = reinterpret_cast<int*>(ws + l.labels);
-  int* cnt = labels + cap_px;
-  hipStream_t st = (hipStream_t)stream;
-  hipLaunchKernelGGL(mr_offsets_kernel, dim3(1), dim3(MR_THREADS), 0, st, windows, R, H, W, cap_px, pix_off, best, nvert, status);
-  GLASS_CHECK_LAUNCH("glass_mask_rings_count (offsets)");
-  const dim3 g(MR_LABEL_GRID_X, grid_masks(R));
-  hipLaunchKernelGGL(mr_label_kernel<MR_INIT>, g, dim3(MR_THREADS), 0, st, masks, R, H, W, windows, pix_off, labels, cnt, best, status);
-  hipLaunchKernelGGL(mr_label_kernel<MR_MERGE>, g, dim3(MR_THREADS), 0, st, masks, R, H, W, windows, pix_off, labels, cnt, best, status);
-  hipLaunchKernelGGL(mr_label_kernel<MR_COUNT>, g, dim3(MR_THREADS), 0, st, masks, R, H, W, windows, pix_off, labels, cnt, best, status);
-  hipLaunchKernelGGL(mr_label_kernel<MR_SELECT>, g, dim3(MR_THREADS), 0, st, masks, R, H, W, windows, pix_off, labels, cnt, best, status);
-  GLASS_CHECK_LAUNCH("glass_mask_rings_count (label)");
-  hipLaunchKernelGGL(mr_trace_kernel<false>, dim3(grid_masks(R)), dim3(MR_THREADS), 0, st, R, H, W, windows, pix_off, cap_px, labels, best,
-                     nvert, (const int*)nullptr, (int2*)nullptr, 0ll, status);
-  GLASS_CHECK_LAUNCH("glass_mask_rings_count (trace)");
-  hipLaunchKernelGGL(mr_ring_offsets_kernel, dim3(1), dim3(MR_THREADS), 0, st, nvert, R, ring_off, status);
-  GLASS_CHECK_LAUNCH("glass_mask_rings_count (ring offsets)");
-  return GLASS_OK;
+  return rings_count("glass_mask_rings_count", R, H, W, windows, workspace, workspace_bytes, ring_off, status, (hipStream_t)stream,
+                     [&](dim3 g, hipStream_t st, const long long* pix_off, int* labels, int* cnt, unsigned long long* best) {
+                       hipLaunchKernelGGL(mr_label_kernel<MR_INIT>, g, dim3(MR_THREADS), 0, st, masks, R, H, W, windows, pix_off, labels,
+                                          cnt, best, status);
+                     });
 }
 
 extern "C" int glass_mask_rings_write(int R, int H, int W, const int* windows, const void* workspace, int64_t workspace_bytes,
@@ -484,4 +621,57 @@ extern "C" int glass_mask_rings_write(int R, int H, int W, const int* windows, c
                      (long long)n_points, status);
   GLASS_CHECK_LAUNCH("glass_mask_rings_write");
   return GLASS_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------- RoI form
+
+namespace {
+
+int roi_args_ok(const char* what, int R, int M, int H, int W, float threshold) {
+  GLASS_CHECK_ARG(sizes_ok(R, H, W), "%s: bad sizes R=%d H=%d W=%d (H, W in 1..65535, H * W < 2^31)", what, R, H, W);
+  GLASS_CHECK_ARG(M >= 1 && M <= 4096, "%s: M=%d (1..4096)", what, M);
+  GLASS_CHECK_ARG(threshold > 0.f, "%s: threshold=%g must be positive (at 0 or below the paste sets the whole image, or is the "
+                  "visualisation mode)", what, (double)threshold);
+  return GLASS_OK;
+}
+
+}  // namespace
+
+extern "C" int glass_roi_mask_rects(const float* boxes, int R, int M, int H, int W, int* rects, glass_stream_t stream) {
+  if (int rc = roi_args_ok("glass_roi_mask_rects", R, M, H, W, 1.f)) return rc;
+  if (R == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(boxes && rects, "glass_roi_mask_rects: null pointer");
+  GLASS_CHECK_ARG(((uintptr_t)rects & 15) == 0, "glass_roi_mask_rects: rects must be 16-byte aligned");
+  hipLaunchKernelGGL(mr_roi_rect_kernel, dim3(cdiv(R, 256)), dim3(256), 0, (hipStream_t)stream, boxes, R, M, H, W,
+                     reinterpret_cast<int4*>(rects));
+  GLASS_CHECK_LAUNCH("glass_roi_mask_rects");
+  return GLASS_OK;
+}
+
+extern "C" int glass_roi_mask_windows(const float* masks, const float* boxes, int R, int M, int H, int W, float threshold,
+                                      int* windows, glass_stream_t stream) {
+  if (int rc = roi_args_ok("glass_roi_mask_windows", R, M, H, W, threshold)) return rc;
+  if (R == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(masks && boxes && windows, "glass_roi_mask_windows: null pointer");
+  GLASS_CHECK_ARG(((uintptr_t)windows & 15) == 0, "glass_roi_mask_windows: windows must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  hipLaunchKernelGGL(mr_window_init_kernel, dim3(cdiv(R, 256)), dim3(256), 0, st, reinterpret_cast<int4*>(windows), R, H, W);
+  GLASS_CHECK_LAUNCH("glass_roi_mask_windows (init)");
+  hipLaunchKernelGGL(mr_roi_window_kernel, dim3(MR_LABEL_GRID_X, grid_masks(R)), dim3(MR_THREADS), 0, st, masks, boxes, R, M, H, W,
+                     threshold, windows);
+  GLASS_CHECK_LAUNCH("glass_roi_mask_windows");
+  return GLASS_OK;
+}
+
+extern "C" int glass_roi_mask_rings_count(const float* masks, const float* boxes, int R, int M, int H, int W, float threshold,
+                                          const int* windows, void* workspace, int64_t workspace_bytes, int* ring_off, int* status,
+                                          glass_stream_t stream) {
+  if (int rc = roi_args_ok("glass_roi_mask_rings_count", R, M, H, W, threshold)) return rc;
+  if (R == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(masks && boxes && windows && workspace && ring_off && status, "glass_roi_mask_rings_count: null pointer");
+  return rings_count("glass_roi_mask_rings_count", R, H, W, windows, workspace, workspace_bytes, ring_off, status, (hipStream_t)stream,
+                     [&](dim3 g, hipStream_t st, const long long* pix_off, int* labels, int* cnt, unsigned long long*) {
+                       hipLaunchKernelGGL(mr_roi_label_init_kernel, g, dim3(MR_THREADS), 0, st, masks, boxes, R, M, H, W, threshold,
+                                          windows, pix_off, labels, cnt, status);
+                     });
 }

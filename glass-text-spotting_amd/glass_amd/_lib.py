@@ -7,8 +7,10 @@ sizes and device addresses whole, and refuses a wrongly typed argument on the ho
 One header per feature: include/glass_hip.h is closed (its set of prototypes, `EXPORTS`, is pinned by the host tests), and
 so is include/glass_hip_ext.h (`EXT_EXPORTS`, the lexicon beam search).  Every later feature declares its entry points in a
 header of its own, include/glass_hip_ext_<feature>.h, which includes the first; `addon_signatures()` parses all of them in
-sorted order and `ADDON_EXPORTS` lists their names (a name declared twice is an error).  `lib()` requires and binds the
-three sets the same way; additions leave `ABI_VERSION` alone.
+sorted order and `ADDON_EXPORTS` lists their names (a name declared twice is an error).  That set is pinned by the host tests
+too (the views header alone), so it is closed as well: a feature after it declares its entry points in
+include/glass_hip_feature_<feature>.h (`feature_signatures()`, `FEATURE_EXPORTS`, same rules), and a test pins only the names
+of its own header.  `lib()` requires and binds the four sets the same way; additions leave `ABI_VERSION` alone.
 
 The product path has NO CPU fallback: `lib()` raises if the shared object is missing or
 does not export every declared symbol, and every op wrapper raises if its tensors are not
@@ -102,27 +104,52 @@ def addon_headers() -> List[str]:
     return sorted(glob.glob(os.path.join(INCLUDE, "glass_hip_ext_*.h")))
 
 
+def _declared_once(paths: List[str], taken: Dict[str, str]) -> Dict[str, Tuple[object, list]]:
+    """`signatures()` of the headers `paths` together; raises for a name in `taken` ({name: header}) or declared by two of them"""
+    sigs: Dict[str, Tuple[object, list]] = {}
+    for path in paths:
+        with open(path) as fh:
+            here = signatures(fh.read())
+        both = sorted(set(here) & set(taken))
+        if both:
+            raise GlassLibraryError(f"include/{os.path.basename(path)} declares {both} again (first in "
+                                    f"include/{taken[both[0]]})")
+        taken.update({n: os.path.basename(path) for n in here})
+        sigs.update(here)
+    return sigs
+
+
 def addon_signatures() -> Dict[str, Tuple[object, list]]:
     """`signatures()` of every include/glass_hip_ext_<feature>.h together; a name that two headers declare (one of them may be
     glass_hip.h or glass_hip_ext.h) raises"""
     global _ADDON_SIGNATURES
     if _ADDON_SIGNATURES is None:
-        sigs: Dict[str, Tuple[object, list]] = {}
         taken = {**{n: "glass_hip.h" for n in signatures()}, **{n: "glass_hip_ext.h" for n in ext_signatures()}}
-        for path in addon_headers():
-            with open(path) as fh:
-                here = signatures(fh.read())
-            both = sorted(set(here) & set(taken))
-            if both:
-                raise GlassLibraryError(f"include/{os.path.basename(path)} declares {both} again (first in "
-                                        f"include/{taken[both[0]]})")
-            taken.update({n: os.path.basename(path) for n in here})
-            sigs.update(here)
-        _ADDON_SIGNATURES = sigs
+        _ADDON_SIGNATURES = _declared_once(addon_headers(), taken)
     return _ADDON_SIGNATURES
 
 
 ADDON_EXPORTS = list(addon_signatures())    # every entry point the per-feature headers declare, header by header
+
+_FEATURE_SIGNATURES: Optional[Dict[str, Tuple[object, list]]] = None
+
+
+def feature_headers() -> List[str]:
+    """the headers include/glass_hip_feature_<feature>.h, in sorted order"""
+    return sorted(glob.glob(os.path.join(INCLUDE, "glass_hip_feature_*.h")))
+
+
+def feature_signatures() -> Dict[str, Tuple[object, list]]:
+    """`signatures()` of every include/glass_hip_feature_<feature>.h together; a name that any other header declares raises"""
+    global _FEATURE_SIGNATURES
+    if _FEATURE_SIGNATURES is None:
+        taken = {**{n: "glass_hip.h" for n in signatures()}, **{n: "glass_hip_ext.h" for n in ext_signatures()},
+                 **{n: "a glass_hip_ext_*.h" for n in addon_signatures()}}
+        _FEATURE_SIGNATURES = _declared_once(feature_headers(), taken)
+    return _FEATURE_SIGNATURES
+
+
+FEATURE_EXPORTS = list(feature_signatures())    # every entry point the glass_hip_feature_*.h headers declare, header by header
 
 
 # Device code is compiled WITHOUT packed-f32 (v_pk_*_f32) and fma_mix instruction selection.  On MI355X / ROCm 7.2 a VOP3P
@@ -198,10 +225,10 @@ def lib() -> ctypes.CDLL:
                 f"{SO_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = ctypes.CDLL(SO_PATH)
-        missing = [s for s in EXPORTS + EXT_EXPORTS + ADDON_EXPORTS if not hasattr(L, s)]
+        missing = [s for s in EXPORTS + EXT_EXPORTS + ADDON_EXPORTS + FEATURE_EXPORTS if not hasattr(L, s)]
         if missing:
             raise GlassLibraryError(f"{SO_PATH} lacks symbols {missing}")
-        for name, (restype, argtypes) in {**signatures(), **ext_signatures(), **addon_signatures()}.items():
+        for name, (restype, argtypes) in {**signatures(), **ext_signatures(), **addon_signatures(), **feature_signatures()}.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = restype, argtypes
         _LIB = L

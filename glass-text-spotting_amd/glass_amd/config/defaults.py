@@ -131,6 +131,12 @@ def add_e2e_config(cfg: CN) -> None:
     cfg.MODEL.ROI_MASK_HEAD.merge_from_other_cfg(
         _recognizer_block(None, "CNN_V1", "BiLSTMBlock", "ASTER"))
     cfg.MODEL.ROI_MASK_HEAD.MASK_INFERENCE = False
+    # MI355X build only (not a reference key), read with MASK_INFERENCE: True = `pred_masks` is the bool [R, H, W] tensor of the
+    # masks pasted over the whole image, as in the reference; False = the instances carry the RoI masks themselves,
+    # `pred_mask_rois` float [R, M, M], and `pred_mask_boxes` [R, 5], the boxes they were predicted in (image pixels), which
+    # `MaskPolygonizer.from_rois` turns into the same polygons: memory no longer grows with detections x image area, and the
+    # two fields pass through GlassRunner.run_batch / run_tiled like any other per-detection row
+    cfg.MODEL.ROI_MASK_HEAD.PASTE_MASKS = True
     blk = _recognizer_block("", "CNN_V1_2", "BiLSTMBlockV2", "ASTER_V2")
     blk.update({"POOLER_TYPE": "ROIAlignRotated", "NORM": "BN", "POOLER_SAMPLING_RATIO": 0,
                 "CONV_DIM": 256, "SAMPLING_RATIO": 0})

@@ -142,7 +142,18 @@ def instances_to_coco_json(instances, file_name, text_encoder, onlyRemoveFirstLa
     """One dict per word with non-empty text and a polygon of >= 3 points (text_evaluator.py:351-415)."""
     if len(instances) == 0:
         return []
-    if instances.has("pred_masks") and masks_to_polygons is not None:
+    if instances.has("pred_mask_rois") and masks_to_polygons is not None:
+        # MODEL.ROI_MASK_HEAD.PASTE_MASKS False: the instances carry the RoI masks and the boxes they were predicted in.  A
+        # callback with `from_rois` (MaskPolygonizer) traces them as they are; any other gets the pasted masks it expects
+        rois, mboxes = instances.pred_mask_rois, instances.pred_mask_boxes
+        mboxes = mboxes.tensor if hasattr(mboxes, "tensor") else mboxes
+        if hasattr(masks_to_polygons, "from_rois"):
+            polygons = masks_to_polygons.from_rois(rois, mboxes, instances.image_size)
+        else:
+            from ..ops import native as K
+            masks = K.paste_rotated_masks(rois.contiguous(), mboxes.contiguous(), instances.image_size, 0.5)
+            polygons = masks_to_polygons(masks if getattr(masks_to_polygons, "takes_device_tensor", False) else masks.cpu().numpy())
+    elif instances.has("pred_masks") and masks_to_polygons is not None:
         masks = instances.pred_masks
         # a callback that declares `takes_device_tensor` (MaskPolygonizer) gets the tensor where it lies
         polygons = masks_to_polygons(masks if getattr(masks_to_polygons, "takes_device_tensor", False) else masks.cpu().numpy())

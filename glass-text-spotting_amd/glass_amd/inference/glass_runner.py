@@ -78,6 +78,13 @@ class GlassRunner:
         u8 = torch.from_numpy(np.ascontiguousarray(original_image)).to(self.device)
         return K.image_u8hwc_to_chw(u8, (nh, nw), flip_channels=(self.input_format == "RGB"))
 
+    @staticmethod
+    def _scaled_boxes(boxes: torch.Tensor, scale_xy: torch.Tensor) -> torch.Tensor:
+        """padded boxes [N, K, 5] times the per-image (sx, sy) [N, 2].  The runner only scales uniformly (sx == sy): centre and
+        extents are multiplied (one float32 product each), the angle is kept."""
+        sx, sy = scale_xy[:, None, 0:1], scale_xy[:, None, 1:2]
+        return torch.cat([boxes[..., 0:1] * sx, boxes[..., 1:2] * sy, boxes[..., 2:3] * sx, boxes[..., 3:4] * sy, boxes[..., 4:5]], -1)
+
     def run_batch(self, images: Sequence[np.ndarray]) -> List[Instances]:
         """Many images per step with per-image results identical to image-by-image calls.  detectron2
         pads a batch to its largest image and the pad region is visible to the backbone/RPN, so images
@@ -108,8 +115,15 @@ class GlassRunner:
                     C = len(self.cfg.MODEL.ROI_RECOGNIZER_HEAD.CHARACTER_SET) + 2
                     text = torch.zeros(tuple(det.scores.shape) + (T, C), dtype=torch.float32, device=self.device)
                 # (BEAM_DISTRIBUTIONS: the full distribution rows are gathered with the survivors, like the orientations)
+                extra = {"orientations": det.orient, "pred_text_dist": getattr(det, "text_dist", None)}
+                rois = getattr(det, "mask_rois", None)
+                if rois is not None:
+                    # MODEL.ROI_MASK_HEAD.PASTE_MASKS False: the mask rows ride along with the boxes they were predicted in,
+                    # scaled to the original image's pixels (the masks' frame; pred_boxes may be enlarged by the merge step)
+                    extra["pred_mask_rois"] = rois
+                    extra["pred_mask_boxes"] = self._scaled_boxes(det.boxes, sc)
                 res = self.post_processor.process_padded(det.boxes, det.scores, det.counts_dev, text, sc, [shapes[i] for i in idxs],
-                                                         {"orientations": det.orient, "pred_text_dist": getattr(det, "text_dist", None)})
+                                                         extra)
                 for i, r in zip(idxs, res):
                     out[i] = r
             else:
@@ -117,6 +131,10 @@ class GlassRunner:
                     preds = res["instances"]
                     if ratios[i] != 1:
                         preds.pred_boxes.scale(1 / ratios[i], 1 / ratios[i])
+                        if preds.has("pred_mask_boxes"):
+                            # PASTE_MASKS False: the masks' frame follows pred_boxes into the original image's pixels (no word
+                            # post-processing on this path, so the two are the same boxes)
+                            preds.pred_mask_boxes = preds.pred_boxes.tensor.clone()
                     preds._image_size = tuple(shapes[i])
                     out[i] = preds
         for r in out:
@@ -136,9 +154,11 @@ class GlassRunner:
         different views).  The merged set - at most 1024 detections - then takes the ordinary way through the word
         post-processor, with the boxes in the original image's pixels."""
         heads = self.model.roi_heads
-        if getattr(heads, "mask_inference", False):
-            raise NotImplementedError("run_tiled: MODEL.ROI_MASK_HEAD.MASK_INFERENCE is on; masks are pasted per tile frame and "
-                                      "merging them is not supported")
+        with_masks = bool(getattr(heads, "mask_inference", False))
+        if with_masks and getattr(self.model, "paste_masks", True):
+            raise NotImplementedError("run_tiled: MODEL.ROI_MASK_HEAD.MASK_INFERENCE is on and the masks are pasted per tile frame, "
+                                      "which cannot be merged; set MODEL.ROI_MASK_HEAD.PASTE_MASKS False to carry the RoI masks "
+                                      "(pred_mask_rois / pred_mask_boxes) instead")
         if getattr(getattr(heads, "recognizer_head", None), "image_segments", None) is not None:
             raise NotImplementedError("run_tiled: the recogniser head carries per-image lexicon segments (image_segments); the "
                                       "views of a tiled image are not images of that list - set the lexicon with one segment")
@@ -203,13 +223,18 @@ class GlassRunner:
         counts = torch.cat([d.counts_dev for d in dets], 0)
         if text is None and sum(sum(d.counts_host) for d in dets) > 0:
             raise RuntimeError("recognizer output missing")
+        # PASTE_MASKS False: the views' mask rows [n, K, M, M] (a call without a detection has none: zeros in its place)
+        rois = None
+        if with_masks:
+            have = [d.mask_rois for d in dets if getattr(d, "mask_rois", None) is not None]
+            rois = joined("mask_rois", tuple(have[0].shape[2:])) if have else None
         # ---- the merge, and the survivors' rows gathered by their source slot
         thr = float(nms_thresh or self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST)
         m = K.merge_views(boxes.contiguous(), scores.contiguous(), counts.contiguous(), K.upload(xform, torch.float32, dev),
                           K.upload(keep, torch.float32, dev), K.upload(band, torch.float32, dev), thr, K.MERGE_VIEWS_MAX_OUT)
         src = m["src"].long()
         gather = lambda t: None if t is None else t.reshape((V * Kdet,) + tuple(t.shape[2:])).index_select(0, src).unsqueeze(0)
-        orient, text, text_dist = gather(orient), gather(text), gather(text_dist)
+        orient, text, text_dist, rois = gather(orient), gather(text), gather(text_dist), gather(rois)
         n_out, truncated = m["count"].tolist()                      # the one read of out_count
         if truncated:
             self.logger.warning(f"run_tiled: more than {K.MERGE_VIEWS_MAX_OUT} merged detections; the lowest-scored are cut off")
@@ -217,8 +242,13 @@ class GlassRunner:
             if text is None:          # no detections in any view
                 text = torch.zeros((1, K.MERGE_VIEWS_MAX_OUT, T, C), dtype=torch.float32, device=dev)
             sc = torch.tensor([[1.0 / scale, 1.0 / scale]], dtype=torch.float32).to(dev)
+            extra = {"orientations": orient, "pred_text_dist": text_dist}
+            if rois is not None:
+                # the masks' frame: the merged boxes, before word post-processing, in the original image's pixels
+                extra["pred_mask_rois"] = rois
+                extra["pred_mask_boxes"] = self._scaled_boxes(m["boxes"].unsqueeze(0), sc)
             res = self.post_processor.process_padded(m["boxes"].unsqueeze(0), m["scores"].unsqueeze(0), m["count"][:1], text, sc,
-                                                     [(height, width)], {"orientations": orient, "pred_text_dist": text_dist})[0]
+                                                     [(height, width)], extra)[0]
         else:
             res = Instances((height, width))
             res.pred_boxes = RotatedBoxes(m["boxes"][:n_out])
@@ -229,6 +259,11 @@ class GlassRunner:
                     res.set(name, t[0, :n_out])
             if scale != 1:
                 res.pred_boxes.scale(1 / scale, 1 / scale)
+            if rois is not None:
+                # no word post-processing here: the masks' frame is pred_boxes as they now stand, in original pixels (a copy,
+                # taken AFTER the in-place scale above, which also went through m["boxes"])
+                res.pred_mask_rois = rois[0, :n_out]
+                res.pred_mask_boxes = res.pred_boxes.tensor.clone()
         self.logger.info(f"Tiled inference: {len(plan.tiles)} tiles{' + the full view' if with_full else ''}, {n_out} merged "
                          f"detections, {len(res)} word instances")
         return res

@@ -51,6 +51,8 @@ class GeneralizedRCNN(InferenceModule):
         # kernel routing of THIS model (precision from the cfg, the A/B switches from the GLASS_* environment read here, once):
         # stamped on every ConvWeight at load, read by the launches - nothing process-global (SURVEY 8b "Threading")
         self.routing = K.Routing(precision=self.conv_precision)
+        # MASK_INFERENCE only: paste the RoI masks over the image (the reference), or hand them on as they are
+        self.paste_masks = bool(getattr(getattr(cfg.MODEL, "ROI_MASK_HEAD", None), "PASTE_MASKS", True))
         self._loaded = False
         # padded device-resident results of the most recent synchronous call.  With several steps in flight
         # (utils.pipeline.run_pipelined) read `.batch` of the step's own return value (pipeline.StepOutput) instead.
@@ -234,6 +236,7 @@ class GeneralizedRCNN(InferenceModule):
         post = BatchedDetections(ob, os_, oo, oc, counts, out_sizes)
         post.text = ot
         post.text_dist = od
+        post.mask_rois = om if not self.paste_masks else None      # PASTE_MASKS False: the finalized mask rows [N, K, M, M]
         self.last_batch = post
         results = post.to_instances()
         if om is not None:
@@ -241,7 +244,11 @@ class GeneralizedRCNN(InferenceModule):
             # scaled once more unless filter_small_boxes' indexing broke its alias with pred_boxes
             for n, r in enumerate(results):
                 c = counts[n]
-                r.pred_masks = K.paste_rotated_masks(om[n, :c].contiguous(), ob[n, :c].contiguous(), out_sizes[n], 0.5)
+                if self.paste_masks:
+                    r.pred_masks = K.paste_rotated_masks(om[n, :c].contiguous(), ob[n, :c].contiguous(), out_sizes[n], 0.5)
+                else:
+                    r.pred_mask_rois = om[n, :c].contiguous()
+                    r.pred_mask_boxes = ob[n, :c].clone()
                 rb = RotatedBoxes(ob[n, :c].clone())
                 if not self._filter_small:
                     rb.scale(sxy[n][0], sxy[n][1])
@@ -256,7 +263,7 @@ class GeneralizedRCNN(InferenceModule):
         for r, inp, image_size in zip(instances, batched_inputs, image_sizes):
             height = inp.get("height", image_size[0])
             width = inp.get("width", image_size[1])
-            out.append({"instances": detector_postprocess(r, height, width)})
+            out.append({"instances": detector_postprocess(r, height, width, paste_masks=self.paste_masks)})
         return out
 
 
@@ -286,7 +293,7 @@ class GlassRCNN(GeneralizedRCNN):
                 r = self.post_processor.resize_boxes(r, self.inflate_ratio)
             if self.drop_overlapping_boxes:
                 r = self.post_processor.drop_overlapping_boxes(r, self.ioa_threshold, self.valid_score)
-            out.append({"instances": detector_postprocess(r, height, width)})
+            out.append({"instances": detector_postprocess(r, height, width, paste_masks=self.paste_masks)})
         return out
 
     def _postprocess_batched_g(self, det, batched_inputs, image_sizes):

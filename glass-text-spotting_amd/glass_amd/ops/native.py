@@ -1913,6 +1913,119 @@ def mask_rings(masks: torch.Tensor):
     return xy, meta[:R + 1]
 
 
+ROI_MASK_RECT_MARGIN = 2          # pixels added on every side of the candidate rectangle (PASTE_RECT_MARGIN, csrc/mask_paste_common.h)
+
+
+def roi_mask_rects(boxes, M: int, image_hw: Tuple[int, int], margin: int = ROI_MASK_RECT_MARGIN) -> np.ndarray:
+    """The candidate rectangle of every box, on the host in float64: int32 [R, 4] = (x0, y0, x1, y1) inclusive, x1 < x0 for
+    "empty".  `paste_rotated_masks` cannot set a pixel outside it: a pasted pixel is non-zero only where its centre p + 0.5 lies
+    in the rotated box inflated by 1 + 1/M (grid_sample with zero padding has no tap once floor(fx) leaves [-1, M)), i.e. in
+    [c - e, c + e] with A = |w|/2 (1 + 1/M), B = |h|/2 (1 + 1/M), ex = A|cos| + B|sin|, ey = A|sin| + B|cos|.  Widened by
+    `margin` pixels on every side (the paste rounds in float32), then clipped to the image.  A box with a non-finite component
+    gives the empty rectangle (the paste yields all zeros there too).
+    This is the statement the tests hold the paste to.  The kernels of `roi_mask_rings` compute their rectangle themselves,
+    on the device, by the same formula (glass_roi_mask_rects shows it); the two need not be equal, each contains the support."""
+    b = np.asarray(boxes.detach().cpu().numpy() if isinstance(boxes, torch.Tensor) else boxes, dtype=np.float32).reshape(-1, 5)
+    H, W = int(image_hw[0]), int(image_hw[1])
+    out = np.empty((len(b), 4), dtype=np.int32)
+    out[:] = (W, H, -1, -1)
+    ang = (b[:, 4] * np.float32(0.017453292519943295)).astype(np.float64)      # deg2rad in float32, as the paste does
+    with np.errstate(all="ignore"):
+        ok = np.isfinite(b).all(axis=1) & np.isfinite(ang)
+        b64 = b.astype(np.float64)
+        cs, sn = np.abs(np.cos(ang)), np.abs(np.sin(ang))
+        grow = 1.0 + 1.0 / float(M)
+        A, B = np.abs(b64[:, 2]) * 0.5 * grow, np.abs(b64[:, 3]) * 0.5 * grow
+        ex, ey = A * cs + B * sn, A * sn + B * cs
+        x0 = np.maximum(np.ceil(b64[:, 0] - ex - 0.5) - margin, 0.0)
+        y0 = np.maximum(np.ceil(b64[:, 1] - ey - 0.5) - margin, 0.0)
+        x1 = np.minimum(np.floor(b64[:, 0] + ex - 0.5) + margin, W - 1.0)
+        y1 = np.minimum(np.floor(b64[:, 1] + ey - 0.5) + margin, H - 1.0)
+        ok &= (x0 <= x1) & (y0 <= y1)
+    for k, v in enumerate((x0, y0, x1, y1)):
+        out[ok, k] = v[ok].astype(np.int32)
+    return out
+
+
+def _roi_mask_args(masks: torch.Tensor, boxes: torch.Tensor, image_hw, threshold: float, what: str):
+    _f32c(masks, "masks"); _f32c(boxes, "boxes")
+    if masks.dim() != 3 or masks.shape[1] != masks.shape[2] or masks.shape[1] < 1 or masks.shape[1] > 4096:
+        raise GlassLibraryError(f"{what}: masks must be float32 [R, M, M] with M in 1..4096 (got {tuple(masks.shape)})")
+    R, M = int(masks.shape[0]), int(masks.shape[1])
+    if tuple(boxes.shape) != (R, 5) or boxes.device != masks.device:
+        raise GlassLibraryError(f"{what}: boxes must be float32 [{R}, 5] on the masks' device (got {tuple(boxes.shape)} on {boxes.device})")
+    H, W = int(image_hw[0]), int(image_hw[1])
+    if not (1 <= H <= 65535 and 1 <= W <= 65535 and H * W < 2 ** 31):
+        raise GlassLibraryError(f"{what}: image of {H} x {W}: H, W must be in 1..65535 and H * W < 2^31")
+    threshold = float(threshold)
+    if not threshold > 0:
+        raise GlassLibraryError(f"{what}: threshold={threshold} must be positive (at 0 or below the paste sets the whole image, "
+                                "or is the visualisation mode)")
+    return R, M, H, W, threshold
+
+
+def roi_mask_device_rects(boxes: torch.Tensor, M: int, image_hw: Tuple[int, int]) -> torch.Tensor:
+    """int32 [R, 4]: the candidate rectangles as the kernels of `roi_mask_rings` compute them (glass_roi_mask_rects)"""
+    _dev(boxes, "boxes"); _f32c(boxes, "boxes")
+    if boxes.dim() != 2 or boxes.shape[1] != 5:
+        raise GlassLibraryError(f"roi_mask_device_rects: boxes must be float32 [R, 5] (got {tuple(boxes.shape)})")
+    R, H, W = int(boxes.shape[0]), int(image_hw[0]), int(image_hw[1])
+    rects = torch.empty((R, 4), dtype=torch.int32, device=boxes.device)
+    if R:
+        check(lib().glass_roi_mask_rects(boxes.data_ptr(), R, int(M), H, W, rects.data_ptr(), stream_handle()), "glass_roi_mask_rects")
+    return rects
+
+
+def roi_mask_windows(masks: torch.Tensor, boxes: torch.Tensor, image_hw: Tuple[int, int], threshold: float = 0.5) -> torch.Tensor:
+    """int32 [R, 4]: the windows glass_mask_windows would find in `paste_rotated_masks(masks, boxes, image_hw, threshold)`,
+    from the RoI masks (glass_roi_mask_windows); x1 < x0 for an empty mask"""
+    _dev(masks, "masks"); _dev(boxes, "boxes")
+    R, M, H, W, threshold = _roi_mask_args(masks, boxes, image_hw, threshold, "roi_mask_windows")
+    win = torch.empty((R, 4), dtype=torch.int32, device=masks.device)
+    if R:
+        check(lib().glass_roi_mask_windows(masks.data_ptr(), boxes.data_ptr(), R, M, H, W, threshold, win.data_ptr(), stream_handle()),
+              "glass_roi_mask_windows")
+    return win
+
+
+def roi_mask_rings(masks: torch.Tensor, boxes: torch.Tensor, image_hw: Tuple[int, int], threshold: float = 0.5):
+    """`mask_rings(paste_rotated_masks(masks, boxes, image_hw, threshold))` without the bool [R, H, W] tensor: masks float32
+    [R, M, M] (probabilities) and boxes float32 [R, 5] on the device -> the same (xy int32 [V, 2], ring_off int32 [R + 1]), bit for
+    bit (glass_roi_mask_windows / glass_roi_mask_rings_count / glass_mask_rings_write, csrc/mask_rings.hip).  Whether a pixel is
+    set is the paste's own arithmetic, evaluated inside each box's candidate rectangle (computed on the device) for the
+    windows and inside the windows for the labels; device memory is 8 bytes per window pixel, whatever the image's size.
+    The host waits twice, as in `mask_rings`: for the windows and for the vertex total.  R == 0 launches nothing.
+    Bit-equality with the two-step path holds for boxes at image scale (what `detector_postprocess` leaves, clipped to the
+    image): the rectangle's 2-pixel margin covers the paste's float32 rounding while one float32 ulp of the box's centre and
+    extents stays well below a pixel (|cx|, |cy|, |w|, |h| up to about 2^20); beyond that the float32 paste may set pixels
+    outside the float64 rectangle and the rings may differ.  Memory safety does not depend on it."""
+    _dev(masks, "masks"); _dev(boxes, "boxes")
+    R, M, H, W, threshold = _roi_mask_args(masks, boxes, image_hw, threshold, "roi_mask_rings")
+    dev = masks.device
+    if R == 0:
+        return torch.empty((0, 2), dtype=torch.int32, device=dev), upload([0], torch.int32, dev)
+    L_ = lib()
+    st = stream_handle()
+    win = torch.empty((R, 4), dtype=torch.int32, device=dev)
+    check(L_.glass_roi_mask_windows(masks.data_ptr(), boxes.data_ptr(), R, M, H, W, threshold, win.data_ptr(), st),
+          "glass_roi_mask_windows")
+    win_host = win.cpu()                                               # the host waits: the windows size the workspace
+    ws_bytes = int(L_.glass_mask_rings_workspace_bytes(win_host.data_ptr(), R, H, W))
+    ws = torch.empty((ws_bytes // 8,), dtype=torch.int64, device=dev)
+    meta = torch.empty((R + 2,), dtype=torch.int32, device=dev)        # ring_off [R + 1] | status
+    status = meta.data_ptr() + 4 * (R + 1)
+    check(L_.glass_roi_mask_rings_count(masks.data_ptr(), boxes.data_ptr(), R, M, H, W, threshold, win.data_ptr(), ws.data_ptr(),
+                                        ws_bytes, meta.data_ptr(), status, st), "glass_roi_mask_rings_count")
+    total, code = (int(v) for v in meta[R:].cpu())                     # the host waits: the vertex total sizes xy
+    if code != 0:
+        raise GlassLibraryError(f"glass_roi_mask_rings_count: status {code} (2 short workspace, 3 unclosed walk, 4 too many vertices)")
+    xy = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    if total:
+        check(L_.glass_mask_rings_write(R, H, W, win.data_ptr(), ws.data_ptr(), ws_bytes, meta.data_ptr(), xy.data_ptr(), total,
+                                        status, st), "glass_mask_rings_write")
+    return xy, meta[:R + 1]
+
+
 RING_CHECK_MAX_COORD = 1 << 20    # glass_ring_check (include/glass_hip.h): |coordinate| and points per ring up to here keep
 RING_CHECK_MAX_POINTS = 1 << 20   # every determinant and shoelace sum exact in int64
 

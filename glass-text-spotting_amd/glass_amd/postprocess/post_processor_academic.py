@@ -114,7 +114,7 @@ class PostProcessorAcademic(PostProcessorRotatedBoxes):
         return preds[keep.to(preds.pred_boxes.device) if len(text_scores) else torch.zeros((0,), dtype=torch.bool)]
 
 
-def detector_postprocess(results: Instances, output_height, output_width, mask_threshold=0.5) -> Instances:
+def detector_postprocess(results: Instances, output_height, output_width, mask_threshold=0.5, paste_masks=True) -> Instances:
     ow = output_width.float() if isinstance(output_width, torch.Tensor) else output_width
     oh = output_height.float() if isinstance(output_height, torch.Tensor) else output_height
     scale_x, scale_y = ow / results.image_size[1], oh / results.image_size[0]
@@ -128,7 +128,13 @@ def detector_postprocess(results: Instances, output_height, output_width, mask_t
     output_boxes.scale(scale_x, scale_y)
     output_boxes.clip(results.image_size)
     results = results[output_boxes.nonempty()]
-    if results.has("pred_masks"):          # reference :167-173: paste_masks_in_image on the scaled rotated boxes
+    if results.has("pred_masks") and not paste_masks:
+        # MODEL.ROI_MASK_HEAD.PASTE_MASKS False: the RoI masks and a COPY of the boxes the paste would have used (the word
+        # post-processor's merge step enlarges pred_boxes later; the mask's frame must not move with it)
+        results.pred_mask_rois = results.pred_masks[:, 0, :, :].contiguous()
+        results.pred_mask_boxes = results.pred_boxes.tensor.clone()
+        results.remove("pred_masks")
+    elif results.has("pred_masks"):        # reference :167-173: paste_masks_in_image on the scaled rotated boxes
         from ..ops import native as K
         results.pred_masks = K.paste_rotated_masks(results.pred_masks[:, 0, :, :].contiguous(),
                                                    results.pred_boxes.tensor.contiguous(), results.image_size,
