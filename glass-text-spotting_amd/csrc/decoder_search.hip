@@ -1,0 +1,615 @@
+// Searches over the attention-GRU decoder of decoder.hip, each behind one ABI call with no host synchronisation: beam search,
+// forced decoding (the symbols given) and the lexicon-constrained beam search.  Per step they run the decoder's GRU launch
+// (dec_gru_step) on all rows and one step kernel, one workgroup per item, composed of the rows_* pieces of decoder_common.h.
+#include <type_traits>
+#include "decoder_common.h"
+#include "glass_hip_ext.h"
+
+// ================================================================== beam search (AttentionRecognitionHead.beam_search)
+// The whole search of reference prediction_aster.py:101-222 behind one ABI call: per step dec_gru_kernel on the B*k state rows
+// and beam_step_kernel (one workgroup per batch item), then one beam_backtrack_kernel (one wavefront per item).  No host
+// synchronisation, no read-back; x / xproj stay [B,T,D]: an item's rows are read once per step and serve its k beams.
+//   workspace: hsel [B*k,D] (states gathered by predecessor = the GRU's h_prev) | hraw [B*k,D] (the GRU's output) |
+//              inp [B*k,2D] | score, predecessor and symbol tables [B,L,k] each (predecessors are beam slots 0..k-1)
+// Selection rule (torch.topk leaves ties open): candidates ordered by score descending, then by flat index beam*C + class
+// ascending; -inf candidates last, in index order.
+struct BeamParams {
+  float* sc; int* pr; int* sy;      // decision tables [B][L][k]
+  float* hsel;                      // [B*k][D]
+  int k, L, eos;
+};
+
+// ---- host side, shared by the three searches
+// f(std::integral_constant<int, KB>) with KB = k rounded up to 1, 2, 4, 8 or 16, the row blocking of the step kernels
+template <class F>
+static void with_row_block(int k, F f) {
+  if (k == 1) f(std::integral_constant<int, 1>{});
+  else if (k == 2) f(std::integral_constant<int, 2>{});
+  else if (k <= 4) f(std::integral_constant<int, 4>{});
+  else if (k <= 8) f(std::integral_constant<int, 8>{});
+  else f(std::integral_constant<int, 16>{});
+}
+
+// the limits of a search with k rows per item: `beams` = the rows are k beams, which must also fit the classes; else they are
+// n given sequences
+static int search_limits(const char* fn, bool beams, int B, int k, int T, int D, int C, int max_len) {
+  const char* kn = beams ? "k" : "n";
+  GLASS_CHECK_ARG(D == DEC_D && T > 0 && T <= DEC_TMAX && C > 0 && C <= DEC_CMAX && k >= 1 && k <= BEAM_KMAX && (!beams || k <= C) &&
+                      max_len >= 1 && max_len <= BEAM_LMAX && B >= 0,
+                  "%s: needs D=256, 1<=T<=64, 1<=C<=256, 1<=%s<=16, %s1<=max_len<=64, B>=0 (got B=%d %s=%d T=%d D=%d C=%d max_len=%d)",
+                  fn, kn, beams ? "k<=C, " : "", B, kn, k, T, D, C, max_len);
+  return GLASS_OK;
+}
+
+// the workspace of the two beam searches as byte offsets, hsel | hraw | inp | sc | pr | sy (| end: the lexicon search's node
+// table): the *_workspace_bytes functions and beam_carve both read it
+struct BeamLayout { size_t hsel, hraw, inp, sc, pr, sy, end; };
+static BeamLayout beam_layout(int B, int k, int D, int L) {
+  const size_t state = (size_t)B * k * D * sizeof(float), table = (size_t)B * L * k * sizeof(float);   // int tables: as large
+  BeamLayout o;
+  o.hsel = 0; o.hraw = o.hsel + state; o.inp = o.hraw + state; o.sc = o.inp + 2 * state; o.pr = o.sc + table; o.sy = o.pr + table;
+  o.end = o.sy + table;
+  return o;
+}
+// p.h0 = hsel (the GRU's h_prev), p.h1 = hraw (its output), p.inp and the tables of bp point into `workspace`
+static BeamParams beam_carve(void* workspace, const BeamLayout& o, int k, int L, int eos, DecParams& p) {
+  char* ws = static_cast<char*>(workspace);
+  p.h0 = reinterpret_cast<float*>(ws + o.hsel); p.h1 = reinterpret_cast<float*>(ws + o.hraw); p.inp = reinterpret_cast<float*>(ws + o.inp);
+  BeamParams bp;
+  bp.sc = reinterpret_cast<float*>(ws + o.sc); bp.pr = reinterpret_cast<int*>(ws + o.pr); bp.sy = reinterpret_cast<int*>(ws + o.sy);
+  bp.hsel = p.h0; bp.k = k; bp.L = L; bp.eos = eos;
+  return bp;
+}
+
+// step == -1: only the attention part with h = 0, y = 0 ([GO]) -> inp rows of step 0; step >= 0: fc + log-softmax + running
+// score + top-k of the item's k*C candidates -> tables[step], then (unless it is the last step) predecessor gather of the
+// states and the attention / embedding part for step + 1.  The fc / sEmbed mat-vecs, the energies and the two reductions are
+// dec_fc_att_kernel's, element for element, so the logits are those of glass_attention_decode_step on inflated inputs.
+// KB = k rounded up to 1, 2, 4, 8 or 16 (rows >= k are zero and never written out).
+template <int KB>
+__global__ __launch_bounds__(256) void beam_step_kernel(DecParams p, BeamParams bp, const float* __restrict__ hraw, int step) {
+  __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
+  __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
+  __shared__ float cand[KB][DEC_CMAX];
+  __shared__ float energy[KB][DEC_TMAX];
+  __shared__ float run[KB];
+  __shared__ int ysel[KB], psel[KB];
+  __shared__ float wbest[2][4];
+  __shared__ int wbesti[2][4];
+  const int u = threadIdx.x, b = blockIdx.x, lane = u & 63, wave = u >> 6;
+  const int C = p.C, k = bp.k, L = bp.L;
+  const long row0 = (long)b * k;
+  rows_load<KB>(hraw, row0, k, step, u, h);
+  if (u < KB) {
+    ysel[u] = 0;
+    psel[u] = 0;
+    float rs = -INFINITY;
+    if (u < k) {
+      if (step <= 0) rs = u == 0 ? 0.f : -INFINITY;
+      else {
+        const long i = ((long)b * L + (step - 1)) * k + u;
+        rs = bp.sy[i] == bp.eos ? -INFINITY : bp.sc[i];
+      }
+    }
+    run[u] = rs;
+  }
+  __syncthreads();
+  if (step >= 0) {
+    rows_fc<KB>(p, C, u, h, cand);
+    __syncthreads();
+    rows_score<KB>(k, C, lane, wave, run, cand);
+    __syncthreads();
+    rows_topk<KB>(k, C, u, lane, wave, ~0u, cand, wbest, wbesti, [&](int j, float score, int beam, int cls) {
+      const long i = ((long)b * L + step) * k + j;
+      bp.sc[i] = score; bp.pr[i] = beam; bp.sy[i] = cls;
+      ysel[j] = cls; psel[j] = beam;
+    });
+    if (step + 1 >= L) return;
+    __syncthreads();
+    rows_follow<KB>(k, row0, u, psel, h, bp.hsel);
+  }
+  rows_attend<KB>(p, b, k, row0, u, h, sproj, energy, ysel);
+}
+
+// rank of slot `i` among v[0..k) by value descending, then slot ascending (-inf entries last, in slot order)
+__device__ __forceinline__ int beam_rank(const float* v, int k, int i) {
+  int rank = 0;
+  const float vi = v[i];
+  for (int j = 0; j < k; ++j) rank += (v[j] > vi || (v[j] == vi && j < i)) ? 1 : 0;
+  return rank;
+}
+
+// The reference's back-tracking (prediction_aster.py:161-222), one wavefront per item, lane r = result slot r: the last
+// step's beams sorted, the backward pass with "an ended sequence replaces the worst slot" (slot k - found % k - 1, <eos>
+// entries of a step taken from the highest beam down), the final re-sort.  Path rows of the best hypothesis: row t < length
+// holds exp(score_t - score_{t-1}) at its symbol along the hypothesis's own ancestor chain, every other entry zero.
+__global__ __launch_bounds__(64) void beam_backtrack_kernel(BeamParams bp, int C, int* __restrict__ out_sym,
+                                                            float* __restrict__ out_sc, int* __restrict__ out_len,
+                                                            float* __restrict__ out_path) {
+  __shared__ int p_sym[BEAM_LMAX][BEAM_KMAX];
+  __shared__ int p_idx[BEAM_LMAX][BEAM_KMAX];
+  __shared__ float s_s[BEAM_KMAX];
+  __shared__ int s_len[BEAM_KMAX], s_ord[BEAM_KMAX];
+  const int b = blockIdx.x, lane = threadIdx.x, k = bp.k, L = bp.L;
+  // the item's decision tables, staged once: the backward pass reads them in a dependent chain
+  __shared__ float sc[BEAM_LMAX * BEAM_KMAX];
+  __shared__ int pr[BEAM_LMAX * BEAM_KMAX], sy[BEAM_LMAX * BEAM_KMAX];
+  for (int i = lane; i < L * k; i += 64) {
+    sc[i] = bp.sc[(long)b * L * k + i];
+    pr[i] = bp.pr[(long)b * L * k + i];
+    sy[i] = bp.sy[(long)b * L * k + i];
+  }
+  __syncthreads();
+  if (lane < k) s_s[lane] = sc[(L - 1) * k + lane];
+  __syncthreads();
+  if (lane < k) s_ord[beam_rank(s_s, k, lane)] = lane;
+  __syncthreads();
+  float s = 0.f;
+  int tp = 0, len = L, found = 0;
+  if (lane < k) { tp = s_ord[lane]; s = s_s[tp]; }
+  for (int t = L - 1; t >= 0; --t) {
+    int cur = 0, idx = 0;
+    if (lane < k) { idx = tp; cur = sy[t * k + tp]; tp = pr[t * k + tp]; }
+    for (int j = k - 1; j >= 0; --j) {
+      const int symj = sy[t * k + j];
+      if (symj == bp.eos) {
+        const int res = k - (found % k) - 1;
+        ++found;
+        if (lane == res) { tp = pr[t * k + j]; cur = symj; idx = j; s = sc[t * k + j]; len = t + 1; }
+      }
+    }
+    if (lane < k) { p_sym[t][lane] = cur; p_idx[t][lane] = idx; }
+  }
+  __syncthreads();
+  if (lane < k) { s_s[lane] = s; s_len[lane] = len; }
+  __syncthreads();
+  if (lane < k) s_ord[beam_rank(s_s, k, lane)] = lane;
+  __syncthreads();
+  for (int i = lane; i < k * L; i += 64) {
+    const int r = i / L, t = i - r * L;
+    out_sym[((long)b * k + r) * L + t] = p_sym[t][s_ord[r]];
+  }
+  if (lane < k) {
+    out_sc[(long)b * k + lane] = s_s[s_ord[lane]];
+    out_len[(long)b * k + lane] = s_len[s_ord[lane]];
+  }
+  if (out_path == nullptr) return;
+  float* op = out_path + (long)b * L * C;
+  for (int i = lane; i < L * C; i += 64) op[i] = 0.f;
+  __syncthreads();
+  const int slot = s_ord[0];
+  if (lane < s_len[slot] && s_s[slot] > -INFINITY) {
+    const int t = lane;
+    const float cur = sc[t * k + p_idx[t][slot]];
+    const float prev = t > 0 ? sc[(t - 1) * k + p_idx[t - 1][slot]] : 0.f;
+    op[(long)t * C + p_sym[t][slot]] = expf(cur - prev);
+  }
+}
+
+extern "C" int64_t glass_beam_search_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  (void)T; (void)C;
+  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
+  return (int64_t)beam_layout(B, k, D, max_len).end;
+}
+
+extern "C" int glass_beam_search(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
+                                 int C, int max_len, int eos, int* out_symbols, float* out_scores, int* out_lengths,
+                                 float* out_path_probs, void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
+  if (int rc = search_limits("glass_beam_search", true, B, k, T, D, C, max_len)) return rc;
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && workspace, "glass_beam_search: null pointer");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_workspace_bytes(B, k, T, D, C, max_len),
+                  "glass_beam_search: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_beam_search_workspace_bytes(B, k, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
+  const BeamParams bp = beam_carve(workspace, beam_layout(B, k, D, max_len), k, max_len, eos, p);
+  float *hsel = p.h0, *hraw = p.h1;
+  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_beam_search: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B);
+  auto beam_step = [&](int step) {
+    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL(beam_step_kernel<decltype(kb)::value>, gb, dim3(256), 0, s, p, bp, hraw, step); });
+  };
+  beam_step(-1);                                                                  // attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    dec_gru_step(p, hsel, hraw, s);
+    beam_step(step);
+  }
+  GLASS_CHECK_LAUNCH("glass_beam_search");
+  hipLaunchKernelGGL(beam_backtrack_kernel, gb, dim3(64), 0, s, bp, C, out_symbols, out_scores, out_lengths, out_path_probs);
+  GLASS_CHECK_LAUNCH("glass_beam_search(backtrack)");
+  return GLASS_OK;
+}
+
+// ================================================================== forced decoding (AttentionRecognitionHead.forward)
+// The decoder with the emitted symbols GIVEN (reference prediction_aster.py:33-60, teacher forcing): n sequences per item
+// that share the item's x / xproj rows - a word to score, the k hypotheses of a beam search, lexicon candidates.  Per step
+// dec_gru_kernel on the B*n state rows (ping-pong h0 / h1) and forced_step_kernel (one workgroup per item): fc, log-softmax,
+// the records of the step, then attention + embedding of the given symbol for the next step.  No host synchronisation.
+//   workspace: h0 [B*n,D] | h1 [B*n,D] | inp [B*n,2D] | effective length, bad-symbol flag [B*n] each
+// A sequence is computed for t < its effective length; the GRU still runs on every row (rows past their length carry
+// finite junk that is never written out).  A workgroup whose n sequences have all ended only writes the step's zeros.
+struct ForcedParams {
+  const int* targets;               // [B][n][L]
+  const int* lengths;               // [B][n] or null
+  float* step_logp;                 // [B][n][L]
+  float* scores;                    // [B][n]: the running score between the launches, the result after the last one
+  int* out_len;                     // [B][n]
+  float* probs;                     // [B][n][L][C] or null
+  float* logits;                    // [B][n][L][C] or null
+  int* elen;                        // workspace [B*n]: number of steps computed
+  int* bad;                         // workspace [B*n]: 1 = the sequence stopped at a symbol outside [0, C)
+  int n, L, eos;
+};
+
+// step == -1: effective lengths from `lengths` or the first <eos>, scores = 0, and the attention part with h = 0, y = 0 ([GO])
+// -> inp rows of step 0; step >= 0: fc + log-softmax of the GRU's output rows -> the records of row `step` (zeros for a
+// sequence that has ended), then - if any sequence goes on - attention with y = targets[step] -> inp rows of step + 1.
+// A symbol is used as an index (embedding row, log-softmax entry) only after the range check of the step -1 launch, which ends a
+// sequence AT the first symbol outside [0, C) with score -inf; the index is clamped once more where it is used.
+template <int KB>
+__global__ __launch_bounds__(256) void forced_step_kernel(DecParams p, ForcedParams fp, const float* __restrict__ hraw, int step) {
+  __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
+  __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
+  __shared__ float cand[KB][DEC_CMAX];
+  __shared__ float energy[KB][DEC_TMAX];
+  __shared__ int ycur[KB], ysel[KB], slen[KB], sbad[KB];
+  const int u = threadIdx.x, lane = u & 63, wave = u >> 6;
+  const int b = blockIdx.x;
+  const int C = p.C, n = fp.n, L = fp.L;
+  const long row0 = (long)b * n;
+  if (u < KB) {
+    int len = 0, bad = 0, y = 0;
+    if (u < n) {
+      const long row = row0 + u;
+      const int* tg = fp.targets + row * L;
+      if (step < 0) {
+        const bool given = fp.lengths != nullptr;
+        const int lim = given ? min(max(fp.lengths[row], 0), L) : L;
+        len = lim;
+        for (int t = 0; t < lim; ++t) {
+          const int sym = tg[t];
+          if (sym < 0 || sym >= C) { len = t; bad = 1; break; }
+          if (!given && sym == fp.eos) { len = t + 1; break; }
+        }
+        fp.elen[row] = len;
+        fp.bad[row] = bad;
+        fp.out_len[row] = len;
+        fp.scores[row] = (bad && len == 0) ? -INFINITY : 0.f;
+      } else {
+        len = fp.elen[row];
+        bad = fp.bad[row];
+        if (step < len) y = min(max(tg[step], 0), C - 1);
+      }
+    }
+    ycur[u] = y;
+    ysel[u] = (step >= 0 && step + 1 < len) ? y : 0;
+    slen[u] = len;
+    sbad[u] = bad;
+  }
+  __syncthreads();
+  if (step >= 0) {
+    bool now = false, next = false;
+    for (int r = 0; r < n; ++r) { now = now || step < slen[r]; next = next || step + 1 < slen[r]; }
+    if (now) {                                                  // uniform over the workgroup
+#pragma unroll
+      for (int r = 0; r < KB; ++r) h[r][u] = r < n ? hraw[(row0 + r) * DEC_D + u] : 0.f;
+      __syncthreads();
+      rows_fc<KB>(p, C, u, h, cand);
+      __syncthreads();
+    }
+    // ---- the records of row `step`, wavefront per sequence
+    for (int r = wave; r < n; r += 4) {
+      const long rec = (row0 + r) * L + step;
+      const bool live = step < slen[r];
+      float v[DEC_CMAX / 64];
+      float m = 0.f, ls = 0.f;
+      if (live) ls = row_lsm(cand[r], C, lane, v, m);
+#pragma unroll
+      for (int i = 0; i < DEC_CMAX / 64; ++i) {
+        const int cidx = lane + 64 * i;
+        if (cidx < C) {
+          const float l = live ? (v[i] - m) - ls : 0.f;
+          if (fp.probs != nullptr) fp.probs[rec * C + cidx] = live ? expf(l) : 0.f;
+          if (fp.logits != nullptr) fp.logits[rec * C + cidx] = live ? v[i] : 0.f;
+          if (live && cidx == ycur[r]) {
+            fp.step_logp[rec] = l;
+            const float sc = fp.scores[row0 + r] + l;           // fl32(score_{t-1} + step_logp[t]), in step order
+            fp.scores[row0 + r] = (sbad[r] && step + 1 == slen[r]) ? -INFINITY : sc;
+          }
+        }
+      }
+      if (!live && lane == 0) fp.step_logp[rec] = 0.f;
+    }
+    if (!next || step + 1 >= L) return;
+    __syncthreads();
+  } else {
+#pragma unroll
+    for (int r = 0; r < KB; ++r) h[r][u] = 0.f;
+    __syncthreads();
+  }
+  rows_attend<KB>(p, b, n, row0, u, h, sproj, energy, ysel);
+}
+
+extern "C" int64_t glass_forced_decode_workspace_bytes(int B, int n, int T, int D, int C, int max_len) {
+  (void)T; (void)C;
+  if (B <= 0 || n <= 0 || D <= 0 || max_len <= 0) return 0;
+  const size_t rows = (size_t)B * n;
+  return (int64_t)(rows * D * 4 * sizeof(float) + rows * 2 * sizeof(int));
+}
+
+extern "C" int glass_forced_decode(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T, int D,
+                                   int C, int max_len, int eos, const int* targets, const int* lengths, float* out_step_logp,
+                                   float* out_scores, int* out_lengths, float* out_probs, float* out_logits, void* workspace,
+                                   int64_t workspace_bytes, glass_stream_t stream) {
+  if (int rc = search_limits("glass_forced_decode", false, B, n, T, D, C, max_len)) return rc;
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && targets && out_step_logp && out_scores && out_lengths && workspace,
+                  "glass_forced_decode: null pointer");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len),
+                  "glass_forced_decode: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  const size_t rows = (size_t)B * n;
+  DecParams p = dec_params(x, xproj, w, (int)rows, T, C, max_len);
+  float* ws = static_cast<float*>(workspace);
+  p.h0 = ws; p.h1 = ws + rows * D; p.inp = ws + rows * D * 2;
+  ForcedParams fp;
+  fp.targets = targets; fp.lengths = lengths; fp.step_logp = out_step_logp; fp.scores = out_scores; fp.out_len = out_lengths;
+  fp.probs = out_probs; fp.logits = out_logits;
+  fp.elen = reinterpret_cast<int*>(ws + rows * D * 4);
+  fp.bad = fp.elen + rows;
+  fp.n = n; fp.L = max_len; fp.eos = eos;
+  hipError_t e = hipMemsetAsync(p.h0, 0, rows * D * sizeof(float), s);           // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_forced_decode: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B);
+  float* hb[2] = {p.h0, p.h1};
+  auto forced_step = [&](const float* hraw, int step) {
+    with_row_block(n, [&](auto kb) { hipLaunchKernelGGL(forced_step_kernel<decltype(kb)::value>, gb, dim3(256), 0, s, p, fp, hraw, step); });
+  };
+  forced_step(hb[0], -1);                                                         // lengths, and the attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    dec_gru_step(p, hb[step & 1], hb[(step + 1) & 1], s);
+    forced_step(hb[(step + 1) & 1], step);
+  }
+  GLASS_CHECK_LAUNCH("glass_forced_decode");
+  return GLASS_OK;
+}
+
+// ================================================================== lexicon-constrained beam search (glass_hip_ext.h)
+// glass_beam_search with a mask: every slot carries a node of the lexicon's trie, a candidate (beam, class) keeps its score
+// only where the node has a child for the class's fold symbol (or, for <eos>, where a word ends at the node), and the
+// finalisation returns the k best COMPLETED words.  The step is the unconstrained search's: the same rows_* pieces (the top-k with
+// the mask as its `allow` bits) and the same GRU launch.
+//   workspace: that of glass_beam_search | node table [B,L,k] (the slot's node after the step; -1 = dead)
+struct LexParams {
+  const unsigned* child_mask;       // [N][MW]
+  const int* child_base;            // [N]
+  const int* node_word;             // [N]
+  const int* seg_root;              // [S]
+  const int* fold;                  // [C]
+  const int* item_segment;          // [B]
+  int* nd;                          // workspace [B][L][k]
+  int N, S, F, MW;
+};
+
+// beam_step_kernel with the mask.  Thread u owns class u: its k mask words (one per beam) are loaded once per step into the
+// bit set `allow`; the k node ids live in LDS.  After the selection, thread j moves slot j to its child node.
+template <int KB>
+__global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams bp, LexParams lp, const float* __restrict__ hraw,
+                                                       int step) {
+  __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
+  __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
+  __shared__ float cand[KB][DEC_CMAX];
+  __shared__ float energy[KB][DEC_TMAX];
+  __shared__ float run[KB], ssel[KB];
+  __shared__ int ysel[KB], psel[KB], snode[KB];
+  __shared__ float wbest[2][4];
+  __shared__ int wbesti[2][4];
+  const int u = threadIdx.x, b = blockIdx.x, lane = u & 63, wave = u >> 6;
+  const int C = p.C, k = bp.k, L = bp.L;
+  const long row0 = (long)b * k;
+  rows_load<KB>(hraw, row0, k, step, u, h);
+  if (u < KB) {
+    ysel[u] = 0;
+    psel[u] = 0;
+    ssel[u] = -INFINITY;
+    float rs = -INFINITY;
+    int node = -1;
+    if (u < k) {
+      if (step <= 0) {
+        if (u == 0) {
+          rs = 0.f;
+          const int seg = lp.item_segment[b];
+          if (seg >= 0 && seg < lp.S) node = lp.seg_root[seg];
+        }
+      } else {
+        const long i = ((long)b * L + (step - 1)) * k + u;
+        rs = bp.sc[i];
+        node = bp.sy[i] == bp.eos ? -1 : lp.nd[i];
+      }
+      if (node < 0 || node >= lp.N) { node = -1; rs = -INFINITY; }      // a dead slot: no node, never finite again
+    }
+    run[u] = rs;
+    snode[u] = node;
+  }
+  __syncthreads();
+  if (step >= 0) {
+    // ---- the mask of class u against the k nodes: bit r of `allow` = candidate (beam r, class u) may be emitted
+    unsigned allow = 0u;
+    if (u < C) {
+      const bool stop = u == bp.eos;
+      const int f = lp.fold[u];
+      const bool sym = !stop && f >= 0 && f < lp.F;
+#pragma unroll
+      for (int r = 0; r < KB; ++r) {
+        const int node = r < k ? snode[r] : -1;
+        if (node >= 0) {
+          unsigned bit = 0u;
+          if (stop) bit = lp.node_word[node] >= 0 ? 1u : 0u;
+          else if (sym) bit = (lp.child_mask[(long)node * lp.MW + (f >> 5)] >> (f & 31)) & 1u;
+          allow |= bit << r;
+        }
+      }
+    }
+    rows_fc<KB>(p, C, u, h, cand);
+    __syncthreads();
+    rows_score<KB>(k, C, lane, wave, run, cand);
+    __syncthreads();
+    rows_topk<KB>(k, C, u, lane, wave, allow, cand, wbest, wbesti, [&](int j, float score, int beam, int cls) {
+      const long i = ((long)b * L + step) * k + j;
+      bp.sc[i] = score; bp.pr[i] = beam; bp.sy[i] = cls;
+      ysel[j] = cls; psel[j] = beam; ssel[j] = score;
+    });
+    __syncthreads();
+    // ---- slot j follows its symbol into the trie: the child node, the node itself for <eos> (the terminal node, whose word
+    // the finalisation reports), no node for a selected -inf candidate or an index outside the arrays
+    if (u < k) {
+      const int cls = ysel[u], par = snode[psel[u]];
+      int node = -1;
+      if (ssel[u] > -INFINITY && par >= 0) {
+        if (cls == bp.eos) node = par;
+        else {
+          const int f = lp.fold[cls];
+          if (f >= 0 && f < lp.F) {
+            const unsigned* mw = lp.child_mask + (long)par * lp.MW;
+            const int wq = f >> 5;
+            int below = 0;
+            for (int q = 0; q < wq; ++q) below += __popc(mw[q]);
+            below += __popc(mw[wq] & ((1u << (f & 31)) - 1u));
+            const long child = (long)lp.child_base[par] + below;
+            if (child >= 0 && child < lp.N) node = (int)child;
+          }
+        }
+      }
+      lp.nd[((long)b * L + step) * k + u] = node;
+    }
+    if (step + 1 >= L) return;
+    __syncthreads();
+    rows_follow<KB>(k, row0, u, psel, h, bp.hsel);
+  }
+  rows_attend<KB>(p, b, k, row0, u, h, sproj, energy, ysel);
+}
+
+// The k best completed entries of one item, one wavefront per item: an entry (t, slot) is completed when its symbol is <eos>
+// and its score finite; order = score descending, then flat index t*k + slot ascending (t, then slot).  Lane l owns the
+// entries l + 64 i; k rounds of the wavefront arg-max, then lane r walks result r back through the predecessor table.
+__global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams lp, int C, int* __restrict__ out_sym,
+                                                       float* __restrict__ out_sc, int* __restrict__ out_len,
+                                                       int* __restrict__ out_word, float* __restrict__ out_path) {
+  __shared__ float sc[BEAM_LMAX * BEAM_KMAX];
+  __shared__ int pr[BEAM_LMAX * BEAM_KMAX], sy[BEAM_LMAX * BEAM_KMAX], nd[BEAM_LMAX * BEAM_KMAX];
+  __shared__ int res[BEAM_KMAX];
+  __shared__ int p_idx[BEAM_LMAX];            // the slots of result 0 along its ancestor chain
+  const int b = blockIdx.x, lane = threadIdx.x, k = bp.k, L = bp.L, n = L * k;
+  for (int i = lane; i < n; i += 64) {
+    sc[i] = bp.sc[(long)b * n + i];
+    pr[i] = bp.pr[(long)b * n + i];
+    sy[i] = bp.sy[(long)b * n + i];
+    nd[i] = lp.nd[(long)b * n + i];
+  }
+  __syncthreads();
+  unsigned taken = 0u;
+  for (int j = 0; j < k; ++j) {
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+#pragma unroll
+    for (int i = 0; i < BEAM_LMAX * BEAM_KMAX / 64; ++i) {
+      const int e = lane + 64 * i;
+      if (e < n && !((taken >> i) & 1u) && sy[e] == bp.eos) {
+        const float v = sc[e];
+        if (v > -INFINITY && v < INFINITY && (besti == 0x7fffffff || v > best)) { best = v; besti = e; }
+      }
+    }
+    wave_argmax_first(best, besti);
+    if (besti != 0x7fffffff && (besti & 63) == lane) taken |= 1u << (besti >> 6);
+    if (lane == 0) res[j] = besti == 0x7fffffff ? -1 : besti;
+  }
+  __syncthreads();
+  if (lane < k) {
+    const long row = (long)b * k + lane;
+    int* os = out_sym + row * L;
+    const int e = res[lane];
+    if (e < 0) {
+      for (int t = 0; t < L; ++t) os[t] = bp.eos;
+      out_sc[row] = -INFINITY;
+      out_len[row] = 0;
+      out_word[row] = -1;
+    } else {
+      const int t0 = e / k;
+      int slot = e - t0 * k;
+      const int node = nd[e];
+      out_sc[row] = sc[e];
+      out_len[row] = t0 + 1;
+      out_word[row] = (node >= 0 && node < lp.N) ? lp.node_word[node] : -1;
+      for (int t = L - 1; t > t0; --t) os[t] = bp.eos;
+      for (int t = t0; t >= 0; --t) {
+        os[t] = sy[t * k + slot];
+        if (lane == 0) p_idx[t] = slot;
+        slot = min(max(pr[t * k + slot], 0), k - 1);
+      }
+    }
+  }
+  if (out_path == nullptr) return;
+  float* op = out_path + (long)b * L * C;
+  for (int i = lane; i < L * C; i += 64) op[i] = 0.f;
+  __syncthreads();
+  const int e0 = res[0];
+  if (e0 >= 0 && lane <= e0 / k) {
+    const int t = lane;
+    const float cur = sc[t * k + p_idx[t]];
+    const float prev = t > 0 ? sc[(t - 1) * k + p_idx[t - 1]] : 0.f;
+    op[(long)t * C + sy[t * k + p_idx[t]]] = expf(cur - prev);
+  }
+}
+
+extern "C" int64_t glass_beam_search_lexicon_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  (void)T; (void)C;
+  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
+  return (int64_t)(beam_layout(B, k, D, max_len).end + (size_t)B * max_len * k * sizeof(int));
+}
+
+extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
+                                         int D, int C, int max_len, int eos, const uint32_t* child_mask, const int* child_base,
+                                         const int* node_word, const int* seg_root, const int* fold, int N, int S, int F,
+                                         const int* item_segment, int* out_symbols, float* out_scores, int* out_lengths,
+                                         int* out_words, float* out_path_probs, void* workspace, int64_t workspace_bytes,
+                                         glass_stream_t stream) {
+  if (int rc = search_limits("glass_beam_search_lexicon", true, B, k, T, D, C, max_len)) return rc;
+  GLASS_CHECK_ARG(N >= 1 && S >= 1 && F >= 1 && F <= 256, "glass_beam_search_lexicon: needs N>=1, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)",
+                  N, S, F);
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && out_words && workspace,
+                  "glass_beam_search_lexicon: null pointer");
+  GLASS_CHECK_ARG(child_mask && child_base && node_word && seg_root && fold && item_segment,
+                  "glass_beam_search_lexicon: null trie array");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len),
+                  "glass_beam_search_lexicon: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
+  const BeamLayout lay = beam_layout(B, k, D, max_len);
+  const BeamParams bp = beam_carve(workspace, lay, k, max_len, eos, p);
+  float *hsel = p.h0, *hraw = p.h1;
+  LexParams lp;
+  lp.child_mask = child_mask; lp.child_base = child_base; lp.node_word = node_word; lp.seg_root = seg_root; lp.fold = fold;
+  lp.item_segment = item_segment; lp.nd = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.end);
+  lp.N = N; lp.S = S; lp.F = F; lp.MW = (F + 31) / 32;
+  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_beam_search_lexicon: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B);
+  auto lex_step = [&](int step) {
+    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL(lex_step_kernel<decltype(kb)::value>, gb, dim3(256), 0, s, p, bp, lp, hraw, step); });
+  };
+  lex_step(-1);                                                                   // attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    dec_gru_step(p, hsel, hraw, s);
+    lex_step(step);
+  }
+  GLASS_CHECK_LAUNCH("glass_beam_search_lexicon");
+  hipLaunchKernelGGL(lex_final_kernel, gb, dim3(64), 0, s, bp, lp, C, out_symbols, out_scores, out_lengths, out_words,
+                     out_path_probs);
+  GLASS_CHECK_LAUNCH("glass_beam_search_lexicon(final)");
+  return GLASS_OK;
+}

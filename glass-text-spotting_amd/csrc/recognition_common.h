@@ -1,5 +1,5 @@
-// Small device helpers shared by the per-RoI recognition kernels (recognition.hip: one launch per recurrent step;
-// recurrent_persistent.hip: one launch per recurrent layer / per decode).
+// Small device helpers shared by the per-RoI recognition kernels (fusion_attention.hip; bilstm.hip, decoder.hip and
+// decoder_search.hip: one launch per recurrent step; recurrent_persistent.hip: one launch per recurrent layer / per decode).
 #pragma once
 #include "common.h"
 
@@ -78,6 +78,77 @@ __device__ __forceinline__ LstmCell lstm_cell(float pi, float pf, float pg, floa
   r.c = __fmaf_rn(fg, c_prev, ig * gg);
   r.h = og * tanh_fast(r.c);
   return r;
+}
+
+// acc[g][r] += sum_k W[g*gstride + u][k] * vec[r][k] for one output unit `u` per thread, weights in the
+// k-blocked layout (w4[k4 * rows_total + row] = 4 consecutive k of `row`).  L2 latency (~300 ns) is far
+// longer than one k-step of FMAs, so the weight stream runs PF k-steps ahead through a register ring
+// (statically indexed: fully unrolled), with the reload unconditional in the main loop and absent in
+// the tail (a predicated reload would make hipcc wait vmcnt(0) per element).
+template <int G, int RB, int PF>
+__device__ __forceinline__ void stream_matvec(const float4* __restrict__ w4, int rows_total, int gstride, int u, int K4,
+                                              const float* vec, int ldv, float (&acc)[G][RB]) {
+  float4 ring[PF][G];
+#pragma unroll
+  for (int j = 0; j < PF; ++j)
+#pragma unroll
+    for (int g = 0; g < G; ++g) ring[j][g] = w4[(long)j * rows_total + g * gstride + u];
+  int k0 = 0;
+#pragma unroll 1
+  for (; k0 + PF < K4; k0 += PF) {
+#pragma unroll
+    for (int j = 0; j < PF; ++j) {
+      float4 wv[G];
+#pragma unroll
+      for (int g = 0; g < G; ++g) {
+        wv[g] = ring[j][g];
+        ring[j][g] = w4[(long)(k0 + PF + j) * rows_total + g * gstride + u];
+      }
+#pragma unroll
+      for (int r = 0; r < RB; ++r) {
+        const float4 hv = *reinterpret_cast<const float4*>(vec + r * ldv + (k0 + j) * 4);
+#pragma unroll
+        for (int g = 0; g < G; ++g) acc[g][r] += wv[g].x * hv.x + wv[g].y * hv.y + wv[g].z * hv.z + wv[g].w * hv.w;
+      }
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < PF; ++j) {
+#pragma unroll
+    for (int r = 0; r < RB; ++r) {
+      const float4 hv = *reinterpret_cast<const float4*>(vec + r * ldv + (k0 + j) * 4);
+#pragma unroll
+      for (int g = 0; g < G; ++g)
+        acc[g][r] += ring[j][g].x * hv.x + ring[j][g].y * hv.y + ring[j][g].z * hv.z + ring[j][g].w * hv.w;
+    }
+  }
+}
+
+// C[16 rows][16 RoIs] += W[row0 .. row0+16)[0..K) . hs[roi][0..K)^T on v_mfma_f32_16x16x4_f32.
+// W is the plain row-major [rows][K] matrix (nn.LSTM / nn.GRU layout).  Lane l = (row r = l&15,
+// k-quarter q = l>>4) loads 16 bytes = W[row0+r][16S + 4q .. +3] and hs[l&15][16S + 4q .. +3]; MFMA c of
+// super-step S then contracts k = 16S + 4q + c on both operands, so the 16 k of a super-step are all
+// covered once (the order inside the fp32 sum differs from k-ascending, nothing else).
+template <int K>
+__device__ __forceinline__ void mfma_rows16(const float* __restrict__ W, int ldw, int row0, const float* hs, int ldh,
+                                            int lane, f32x4& acc) {
+  const float* wp = W + (long)(row0 + (lane & 15)) * ldw + (lane >> 4) * 4;
+  const float* hp = hs + (lane & 15) * ldh + (lane >> 4) * 4;
+  // all K/16 weight loads of the job are issued before the first MFMA (one L2 round trip per job, not per
+  // super-step); two accumulators halve the dependent-MFMA chain
+  float4 a[K / 16];
+#pragma unroll
+  for (int S = 0; S < K / 16; ++S) a[S] = *reinterpret_cast<const float4*>(wp + S * 16);
+  f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int S = 0; S < K / 16; ++S) {
+    const float4 b = *reinterpret_cast<const float4*>(hp + S * 16);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[S].x, b.x, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[S].y, b.y, acc2, 0, 0, 0);
+    acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[S].z, b.z, acc, 0, 0, 0);
+    acc2 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[S].w, b.w, acc2, 0, 0, 0);
+  }
+  acc += acc2;
 }
 
 // reference early break (prediction_aster.py:91-93): after step i, if every RoI of the call has

@@ -2,7 +2,7 @@
 // state handed between workgroups inside the launch (reference
 // glass/modeling/recognition/recognizer_encoder.py:118-144, nn.LSTM gate order i,f,g,o, zero initial state).
 //
-// recognition.hip runs the same recurrence as T launches per layer (lstm_step_kernel): every step re-streams the 2 x 1 MiB
+// bilstm.hip runs the same recurrence as T launches per layer (lstm_step_kernel): every step re-streams the 2 x 1 MiB
 // recurrent matrix from L2 and pays a kernel boundary, 8-10 us per step for ~1.7 us of matrix-core work.  Here a CHAIN =
 // (group of 16 RoIs, direction) is served by a SET of 8 workgroups; workgroup `ub` of the set owns hidden units
 // [32 ub, 32 ub + 32): its 4 gates x 32 units x 256 slice of W_hh (128 KiB per direction) stays in registers as
@@ -310,7 +310,7 @@ extern "C" int glass_bilstm_recurrence_persistent(const float* xg, const float* 
 
 // ================================================================== greedy attention-GRU decoder, one launch
 // Reference: AttentionRecognitionHead.sample (glass/modeling/recognition/prediction_aster.py:63-99), AttentionUnit :247-266,
-// DecoderUnit :291-302.  recognition.hip runs a decoding step as two launches (dec_fc_att_kernel, dec_gru_kernel) that re-stream
+// DecoderUnit :291-302.  decoder.hip runs a decoding step as two launches (dec_fc_att_kernel, dec_gru_kernel) that re-stream
 // 2.7 MB of weights from L2 per RoI group and step: 24 us per step, 0.64 ms per image of a 7.9 ms one-image step.  Here a
 // group of 16 RoIs is served by a SET of 16 workgroups for all max_len steps; workgroup j of the set owns
 //   * rows [16 j, 16 j + 16) of every matrix that multiplies a vector of ALL 16 RoIs - the three GRU gates (W_hh and the

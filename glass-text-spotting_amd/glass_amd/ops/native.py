@@ -161,7 +161,7 @@ class Routing:
       rnn         the recurrent encoder: (directions, RoI groups) a workgroup of the one-launch-per-layer BiLSTM kernel
                   interleaves - "1x1" (default: shortest chain, 3 % off the one-step-at-a-time latency), "2x1", "2x2",
                   "persistent" = the library's default - or "steps" (GLASS_RNN=steps: one launch per time step,
-                  csrc/recognition.hip); outputs are bit-identical
+                  csrc/bilstm.hip); outputs are bit-identical
       splitk      implicit-GEMM launches with few output pixels and a long K (one image per step: the box head's fc layers on
                   100 rows, res4 / res5 3x3, the 11-row predictors) as a split-K launch + ordered reduction (GLASS_SPLITK=0)
       small_grid  3x3 layers whose F(4x4) grid does not fill the chip pick their Winograd form by rounds x workgroup time,
@@ -1372,21 +1372,34 @@ def attention_decode_step(x: torch.Tensor, xproj: torch.Tensor, weights: dict, h
     return logits, probs, h_out
 
 
+def _search_inputs(who: str, x: torch.Tensor, xproj: torch.Tensor, targets: Optional[torch.Tensor] = None):
+    """the checks `beam_search`, `beam_search_lexicon` and `forced_decode` (its `targets` too) open with -> (B, T, D, device)"""
+    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj")
+    if targets is not None:
+        _i32(targets, "targets")
+    if xproj.shape != x.shape or xproj.device != x.device:
+        raise GlassLibraryError(f"{who}: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
+    B, T, D = x.shape
+    return B, T, D, x.device
+
+
+def _search_outputs(dev, B: int, k: int, L: int, C: int, seq_dtype, path_probs: bool):
+    """-> (per-step rows [B,k,L] of `seq_dtype`, scores [B,k], lengths int32 [B,k], path rows [B,L,C] | None); sizes the library
+    is yet to refuse are clamped to 0"""
+    k, L = max(k, 0), max(L, 0)
+    return (torch.empty((B, k, L), dtype=seq_dtype, device=dev), torch.empty((B, k), dtype=torch.float32, device=dev),
+            torch.empty((B, k), dtype=torch.int32, device=dev),
+            torch.empty((B, L, max(C, 0)), dtype=torch.float32, device=dev) if path_probs else None)
+
+
 def beam_search(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int, eos: int,
                 path_probs: bool = False):
     """the whole beam search on the device (glass_beam_search; reference AttentionRecognitionHead.beam_search): x, xproj
     [B,T,D] un-inflated -> (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k][, path rows [B,max_len,C] of the
     best hypothesis]), all k hypotheses in final order.  No host synchronisation; limits are checked by the library."""
-    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj")
-    if xproj.shape != x.shape or xproj.device != x.device:
-        raise GlassLibraryError(f"beam_search: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
-    B, T, D = x.shape
+    B, T, D, dev = _search_inputs("beam_search", x, xproj)
     k, C, L = int(beam_width), int(num_classes), int(max_len)
-    dev = x.device
-    symbols = torch.empty((B, max(k, 0), max(L, 0)), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    lengths = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    path = torch.empty((B, max(L, 0), max(C, 0)), dtype=torch.float32, device=dev) if path_probs else None
+    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
     w = _decoder_weights(weights)
     nbytes = int(lib().glass_beam_search_workspace_bytes(B, k, T, D, C, L))
     ws = _workspace(nbytes, dev)
@@ -1402,12 +1415,8 @@ def beam_search_lexicon(x: torch.Tensor, xproj: torch.Tensor, weights: dict, bea
     the int F (evaluation.lexicon.LexiconTrie.tensors / .num_fold) - and item_segment int32 [B] on x's device ->
     (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k], words int32 [B,k][, path rows [B,max_len,C]]): the k most
     likely lexicon words of each item's segment, best first.  No host synchronisation; limits are checked by the library."""
-    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj")
-    if xproj.shape != x.shape or xproj.device != x.device:
-        raise GlassLibraryError(f"beam_search_lexicon: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
-    B, T, D = x.shape
+    B, T, D, dev = _search_inputs("beam_search_lexicon", x, xproj)
     k, C, L = int(beam_width), int(num_classes), int(max_len)
-    dev = x.device
     F = int(trie["F"])
     MW = (F + 31) // 32
     arrays = {n: trie.get(n) for n in ("child_mask", "child_base", "node_word", "seg_root", "fold")}
@@ -1433,11 +1442,8 @@ def beam_search_lexicon(x: torch.Tensor, xproj: torch.Tensor, weights: dict, bea
     _i32(item_segment, "item_segment")
     if tuple(item_segment.shape) != (B,) or item_segment.device != dev:
         raise GlassLibraryError(f"beam_search_lexicon: item_segment {tuple(item_segment.shape)} on {item_segment.device} is not [B={B}] on {dev}")
-    symbols = torch.empty((B, max(k, 0), max(L, 0)), dtype=torch.int32, device=dev)
-    scores = torch.empty((B, max(k, 0)), dtype=torch.float32, device=dev)
-    lengths = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    words = torch.empty((B, max(k, 0)), dtype=torch.int32, device=dev)
-    path = torch.empty((B, max(L, 0), max(C, 0)), dtype=torch.float32, device=dev) if path_probs else None
+    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
+    words = torch.empty_like(lengths)
     w = _decoder_weights(weights)
     nbytes = int(lib().glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, L))
     ws = _workspace(nbytes, dev)
@@ -1455,10 +1461,7 @@ def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: 
     [B,T,D] un-inflated, targets int32 [B,n,max_len] and lengths int32 [B,n] (or None: up to and including the first `eos`)
     on x's device -> (step_logp [B,n,max_len], scores [B,n], lengths int32 [B,n], probs [B,n,max_len,C] | None, logits
     [B,n,max_len,C] | None).  No host synchronisation; limits are checked by the library."""
-    _f32c(x, "x"); _f32c(xproj, "xproj"); _dev(x, "x"); _dev(xproj, "xproj"); _i32(targets, "targets")
-    if xproj.shape != x.shape or xproj.device != x.device:
-        raise GlassLibraryError(f"forced_decode: xproj {tuple(xproj.shape)} on {xproj.device} does not match x {tuple(x.shape)} on {x.device}")
-    B, T, D = x.shape
+    B, T, D, dev = _search_inputs("forced_decode", x, xproj, targets)
     C, L = int(num_classes), int(max_len)
     if targets.dim() != 3 or targets.shape[0] != B or targets.shape[2] != L or targets.device != x.device:
         raise GlassLibraryError(f"forced_decode: targets {tuple(targets.shape)} on {targets.device} is not [B={B}, n, max_len={L}] on {x.device}")
@@ -1467,10 +1470,7 @@ def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: 
         _i32(lengths, "lengths")
         if tuple(lengths.shape) != (B, n) or lengths.device != x.device:
             raise GlassLibraryError(f"forced_decode: lengths {tuple(lengths.shape)} on {lengths.device} is not [B={B}, n={n}] on {x.device}")
-    dev = x.device
-    step_logp = torch.empty((B, n, max(L, 0)), dtype=torch.float32, device=dev)
-    scores = torch.empty((B, n), dtype=torch.float32, device=dev)
-    out_len = torch.empty((B, n), dtype=torch.int32, device=dev)
+    step_logp, scores, out_len, _ = _search_outputs(dev, B, n, L, C, torch.float32, False)
     rows = (B, n, max(L, 0), max(C, 0))
     out_probs = torch.empty(rows, dtype=torch.float32, device=dev) if probs else None
     out_logits = torch.empty(rows, dtype=torch.float32, device=dev) if logits else None

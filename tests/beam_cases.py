@@ -44,7 +44,7 @@ def rand_x(B, T, seed, D=256):
 
 
 # (name, B, k, T, max_len, C, seed): the smallest shapes that cross every boundary of the kernels - B 1 / 3 / 17, every row
-# blocking of the beam-step kernel (k 1, 2, 5 -> 8, 16) and k == C, T 7 / 32 / 64 (not a multiple of the 4 wavefronts, half,
+# blocking of the step kernels (k 1, 2, 3 -> 4, 4, 5 -> 8, 16) and k == C, T 7 / 32 / 64 (not a multiple of the 4 wavefronts, half,
 # full), max_len 1 / 26 / 64, C 5 / 97 / 256 (one, two and four 64-lane pieces), and B*k = 512 rows, where the
 # step kernels of the host path take their 2-row blocking.  Seeds: of 100..115 the one with the largest smallest gap in the
 # float64 replay (a property of the inputs and the rule alone, computed on the CPU)
@@ -55,6 +55,8 @@ CASES = [
     ("b3_k5_t7_l26_c5", 3, 5, 7, 26, 5, 104),
     ("b3_k16_t32_l26_c256", 3, 16, 32, 26, 256, 101),
     ("b32_k16_t7_l6_rows512", 32, 16, 7, 6, 97, 114),
+    ("b2_k3_t7_l6_c13", 2, 3, 7, 6, 13, 101),       # the 4-row blocking with one padding row ...
+    ("b2_k4_t7_l6_c13", 2, 4, 7, 6, 13, 102),       # ... and full
 ]
 
 

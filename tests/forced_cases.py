@@ -7,7 +7,7 @@ records of step t < length, zeros from the length on.  The length of a sequence 
 of its first <eos> plus one, else L.
 
 `case_data(case)` builds, once per case of `beam_cases.CASES` (the smallest shapes that cross the kernels' boundaries: B 1 / 3
-/ 17, every row blocking n 1, 2, 5 -> 8, 16, T 7 / 32 / 64, L 1 / 26 / 64, C 5 / 97 / 256, 512 state rows), the inputs and three
+/ 17, every row blocking n 1, 2, 3 -> 4, 4, 5 -> 8, 16, T 7 / 32 / 64, L 1 / 26 / 64, C 5 / 97 / 256, 512 state rows), the inputs and three
 target sets with their float64 results:
   "hyp"      (a) the k hypotheses and lengths of the float64 beam search `beam_cases.replay`;
   "perturb"  (b) seeded perturbations of them, lengths left to the first <eos>: per sequence, in turn, one symbol below the

@@ -109,6 +109,8 @@ def test_all_hypotheses_against_host_path_and_replay(case):
       b3_k5_t7_l26_c5       6.8e-7 | 2.0e-1 | 1.5e+0 || 0      | 1.9e-6 | 1.4e-5
       b3_k16_t32_l26_c256   7.8e-6 | 8.6e-3 | 1.1e-2 || 4.8e-7 | 3.0e-6 | 6.0e-5
       b32_k16_t7_l6_rows512 9.0e-6 | 3.8e-3 | 1.2e-3 || 3.6e-7 | 1.7e-6 | 5.8e-5
+      b2_k3_t7_l6_c13       2.9e-6 | 3.9e-1 | 1.7e+0 || 3.7e-9 | 2.4e-7 | 1.6e-5
+      b2_k4_t7_l6_c13       1.0e-5 | 1.1e+0 | 1.4e+0 || 1.2e-7 | 5.7e-7 | 2.5e-5
     (the float64 column covers all k hypotheses, the host columns the best one; the golden's three cases: 6.9e-6, 6.0e-6,
     1.0e-5 against the reference's scores)"""
     name, B, k, T, L, C, seed = case

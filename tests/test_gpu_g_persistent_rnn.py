@@ -1,5 +1,5 @@
 """The one-launch-per-layer recurrent kernels (csrc/recurrent_persistent.hip) against the one-launch-per-step kernels
-(csrc/recognition.hip) they replace: the arithmetic is the same instruction sequence, so the outputs must be BIT-identical -
+(csrc/bilstm.hip, csrc/decoder.hip) they replace: the arithmetic is the same instruction sequence, so the outputs must be BIT-identical -
 any difference is a hand-off bug (a stale or torn granule), which a tolerance would hide.  The step kernels themselves are
 held to the reference goldens and the oracle in tests/test_gpu_a_stages.py (those tests now run the persistent path, which is
 the default routing; reference: glass/modeling/recognition/recognizer_encoder.py:118-144, prediction_aster.py:63-99).
