@@ -1,6 +1,6 @@
 // Shared by the attention-GRU decoder (decoder.hip: the greedy decode and the single step) and its searches
-// (decoder_search.hip: beam search, forced decoding, lexicon-constrained beam search): limits, the kernel parameter block, the
-// host helpers every entry point uses, and the pieces of one decoder step on the rows of ONE item.
+// (decoder_search.hip: beam search, forced decoding, the lexicon- and pattern-constrained beam searches): limits, the kernel
+// parameter block, the host helpers every entry point uses, and the pieces of one decoder step on the rows of ONE item.
 #pragma once
 #include "recognition_common.h"
 
@@ -28,7 +28,7 @@ DecParams dec_params(const float* x, const float* xproj, const glass_decoder_wei
 // device code, so the kernel is launched from its own translation unit only)
 void dec_gru_step(const DecParams& p, const float* hprev, float* hnext, hipStream_t stream);
 
-// ---- pieces of one decoder step on the KB rows of ONE item (beam_step_kernel / lex_step_kernel: its k beams;
+// ---- pieces of one decoder step on the KB rows of ONE item (beam_step_kernel / con_step_kernel: its k beams;
 // forced_step_kernel: its n given sequences), called by all 256 threads of the workgroup; u = threadIdx.x, lane = u & 63,
 // wave = u >> 6 (rows_score and rows_topk take the kernel's own lane / wave: deriving them again from u cost the KB = 4 kernels
 // 55 VGPRs and a wave per SIMD).  The mat-vecs, the energies and the reductions are dec_fc_att_kernel's arithmetic, element

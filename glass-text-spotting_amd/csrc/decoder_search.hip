@@ -1,9 +1,10 @@
 // Searches over the attention-GRU decoder of decoder.hip, each behind one ABI call with no host synchronisation: beam search,
-// forced decoding (the symbols given) and the lexicon-constrained beam search.  Per step they run the decoder's GRU launch
+// forced decoding (the symbols given) and the constrained beam searches (a lexicon trie, or any DFA).  Per step they run the decoder's GRU launch
 // (dec_gru_step) on all rows and one step kernel, one workgroup per item, composed of the rows_* pieces of decoder_common.h.
 #include <type_traits>
 #include "decoder_common.h"
 #include "glass_hip_ext.h"
+#include "glass_hip_feature_dfa.h"
 
 // ================================================================== beam search (AttentionRecognitionHead.beam_search)
 // The whole search of reference prediction_aster.py:101-222 behind one ABI call: per step dec_gru_kernel on the B*k state rows
@@ -392,12 +393,68 @@ struct LexParams {
   const int* item_segment;          // [B]
   int* nd;                          // workspace [B][L][k]
   int N, S, F, MW;
+  // ---- what con_step_kernel asks of a constraint (DfaParams answers the same questions from its table)
+  // the node of an item's first beam; the caller checks it against N
+  __device__ __forceinline__ int root(int b) const {
+    const int seg = item_segment[b];
+    return (seg >= 0 && seg < S) ? seg_root[seg] : -1;
+  }
+  // may a beam at `node` (inside [0,N)) emit the class: `stop` = it is <eos>, else `sym` = its fold symbol f is inside [0,F)
+  __device__ __forceinline__ unsigned allow_bit(bool stop, bool sym, int f, int node, int step, int L) const {
+    (void)step; (void)L;
+    unsigned bit = 0u;
+    if (stop) bit = node_word[node] >= 0 ? 1u : 0u;
+    else if (sym) bit = (child_mask[(long)node * MW + (f >> 5)] >> (f & 31)) & 1u;
+    return bit;
+  }
+  // the node after fold symbol f (inside [0,F)) from `par` (inside [0,N)); -1 for one outside the arrays
+  __device__ __forceinline__ int follow(int par, int f) const {
+    const unsigned* mw = child_mask + (long)par * MW;
+    const int wq = f >> 5;
+    int below = 0;
+    for (int q = 0; q < wq; ++q) below += __popc(mw[q]);
+    below += __popc(mw[wq] & ((1u << (f & 31)) - 1u));
+    const long child = (long)child_base[par] + below;
+    return (child >= 0 && child < N) ? (int)child : -1;
+  }
 };
 
-// beam_step_kernel with the mask.  Thread u owns class u: its k mask words (one per beam) are loaded once per step into the
-// bit set `allow`; the k node ids live in LDS.  After the selection, thread j moves slot j to its child node.
-template <int KB>
-__global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams bp, LexParams lp, const float* __restrict__ hraw,
+// The constraint of glass_beam_search_dfa (glass_hip_feature_dfa.h): a slot's node is a state of the automaton
+struct DfaParams {
+  const int* next;                  // [N][F]: -1, or target | min(dist[target], 127) << 24
+  const int* accept;                // [N]
+  const int* start;                 // [S]
+  const int* fold;                  // [C]
+  const int* item_segment;          // [B]
+  int* nd;                          // workspace [B][L][k]
+  int N, S, F;
+  __device__ __forceinline__ int root(int b) const {
+    const int seg = item_segment[b];
+    return (seg >= 0 && seg < S) ? start[seg] : -1;
+  }
+  // one load decides a symbol: the transition exists and the string can still be completed, its stop at step L - 1 at the
+  // latest.  The stop itself needs an accepting state and a non-empty string.
+  __device__ __forceinline__ unsigned allow_bit(bool stop, bool sym, int f, int node, int step, int L) const {
+    unsigned bit = 0u;
+    if (stop) bit = (step >= 1 && accept[node] >= 0) ? 1u : 0u;
+    else if (sym) {
+      const int e = next[(long)node * F + f];
+      bit = (e >= 0 && step + 1 + (e >> 24) <= L - 1) ? 1u : 0u;
+    }
+    return bit;
+  }
+  __device__ __forceinline__ int follow(int par, int f) const {
+    const int e = next[(long)par * F + f];
+    const int q = e & 0xffffff;
+    return (e >= 0 && q < N) ? q : -1;
+  }
+};
+
+// beam_step_kernel with the mask of a constraint CP (LexParams: the trie, DfaParams: the automaton).  Thread u owns class u:
+// its k mask words or table entries (one per beam) are loaded once per step into the bit set `allow`; the k node ids live in
+// LDS.  After the selection, thread j moves slot j to its child node / target state.
+template <int KB, class CP>
+__global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams bp, CP lp, const float* __restrict__ hraw,
                                                        int step) {
   __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
   __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
@@ -421,8 +478,7 @@ __global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams b
       if (step <= 0) {
         if (u == 0) {
           rs = 0.f;
-          const int seg = lp.item_segment[b];
-          if (seg >= 0 && seg < lp.S) node = lp.seg_root[seg];
+          node = lp.root(b);
         }
       } else {
         const long i = ((long)b * L + (step - 1)) * k + u;
@@ -445,12 +501,7 @@ __global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams b
 #pragma unroll
       for (int r = 0; r < KB; ++r) {
         const int node = r < k ? snode[r] : -1;
-        if (node >= 0) {
-          unsigned bit = 0u;
-          if (stop) bit = lp.node_word[node] >= 0 ? 1u : 0u;
-          else if (sym) bit = (lp.child_mask[(long)node * lp.MW + (f >> 5)] >> (f & 31)) & 1u;
-          allow |= bit << r;
-        }
+        if (node >= 0) allow |= lp.allow_bit(stop, sym, f, node, step, L) << r;
       }
     }
     rows_fc<KB>(p, C, u, h, cand);
@@ -463,8 +514,8 @@ __global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams b
       ysel[j] = cls; psel[j] = beam; ssel[j] = score;
     });
     __syncthreads();
-    // ---- slot j follows its symbol into the trie: the child node, the node itself for <eos> (the terminal node, whose word
-    // the finalisation reports), no node for a selected -inf candidate or an index outside the arrays
+    // ---- slot j follows its symbol into the trie / automaton: the child node, the node itself for <eos> (the terminal node,
+    // whose word the finalisation reports), no node for a selected -inf candidate or an index outside the arrays
     if (u < k) {
       const int cls = ysel[u], par = snode[psel[u]];
       int node = -1;
@@ -472,15 +523,7 @@ __global__ __launch_bounds__(256) void lex_step_kernel(DecParams p, BeamParams b
         if (cls == bp.eos) node = par;
         else {
           const int f = lp.fold[cls];
-          if (f >= 0 && f < lp.F) {
-            const unsigned* mw = lp.child_mask + (long)par * lp.MW;
-            const int wq = f >> 5;
-            int below = 0;
-            for (int q = 0; q < wq; ++q) below += __popc(mw[q]);
-            below += __popc(mw[wq] & ((1u << (f & 31)) - 1u));
-            const long child = (long)lp.child_base[par] + below;
-            if (child >= 0 && child < lp.N) node = (int)child;
-          }
+          if (f >= 0 && f < lp.F) node = lp.follow(par, f);
         }
       }
       lp.nd[((long)b * L + step) * k + u] = node;
@@ -600,7 +643,7 @@ extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, con
   if (e != hipSuccess) { glass_set_error("glass_beam_search_lexicon: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
   const dim3 gb(B);
   auto lex_step = [&](int step) {
-    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL(lex_step_kernel<decltype(kb)::value>, gb, dim3(256), 0, s, p, bp, lp, hraw, step); });
+    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL((con_step_kernel<decltype(kb)::value, LexParams>), gb, dim3(256), 0, s, p, bp, lp, hraw, step); });
   };
   lex_step(-1);                                                                   // attention for step 0
   for (int step = 0; step < max_len; ++step) {
@@ -611,5 +654,55 @@ extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, con
   hipLaunchKernelGGL(lex_final_kernel, gb, dim3(64), 0, s, bp, lp, C, out_symbols, out_scores, out_lengths, out_words,
                      out_path_probs);
   GLASS_CHECK_LAUNCH("glass_beam_search_lexicon(final)");
+  return GLASS_OK;
+}
+
+// ================================================================== pattern-constrained beam search (glass_hip_feature_dfa.h)
+// glass_beam_search_lexicon with the trie generalised to a DFA over fold symbols: the same step kernel with DfaParams as its
+// constraint, the same workspace, and lex_final_kernel with `accept` in the place of node_word.
+extern "C" int64_t glass_beam_search_dfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  return glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len);
+}
+
+extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
+                                     int C, int max_len, int eos, const int* next, const int* accept, const int* start,
+                                     const int* fold, int N, int S, int F, const int* item_pattern, int* out_symbols,
+                                     float* out_scores, int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
+                                     int64_t workspace_bytes, glass_stream_t stream) {
+  if (int rc = search_limits("glass_beam_search_dfa", true, B, k, T, D, C, max_len)) return rc;
+  GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256,
+                  "glass_beam_search_dfa: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", N, S, F);
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && out_tags && workspace,
+                  "glass_beam_search_dfa: null pointer");
+  GLASS_CHECK_ARG(next && accept && start && fold && item_pattern, "glass_beam_search_dfa: null automaton array");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len),
+                  "glass_beam_search_dfa: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
+  const BeamLayout lay = beam_layout(B, k, D, max_len);
+  const BeamParams bp = beam_carve(workspace, lay, k, max_len, eos, p);
+  float *hsel = p.h0, *hraw = p.h1;
+  DfaParams dp;
+  dp.next = next; dp.accept = accept; dp.start = start; dp.fold = fold; dp.item_segment = item_pattern;
+  dp.nd = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.end);
+  dp.N = N; dp.S = S; dp.F = F;
+  LexParams fin = {};                                                              // what lex_final_kernel reads: nd, N, node_word
+  fin.nd = dp.nd; fin.N = N; fin.node_word = accept;
+  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_beam_search_dfa: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B);
+  auto dfa_step = [&](int step) {
+    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL((con_step_kernel<decltype(kb)::value, DfaParams>), gb, dim3(256), 0, s, p, bp, dp, hraw, step); });
+  };
+  dfa_step(-1);                                                                   // attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    dec_gru_step(p, hsel, hraw, s);
+    dfa_step(step);
+  }
+  GLASS_CHECK_LAUNCH("glass_beam_search_dfa");
+  hipLaunchKernelGGL(lex_final_kernel, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags, out_path_probs);
+  GLASS_CHECK_LAUNCH("glass_beam_search_dfa(final)");
   return GLASS_OK;
 }

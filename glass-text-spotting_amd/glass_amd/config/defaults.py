@@ -148,6 +148,10 @@ def add_e2e_config(cfg: CN) -> None:
     # (glass_forced_decode) adds its FULL per-step distributions as `pred_text_dist` [Ri,L,C] - what the weighted lexicon
     # protocol reads (`character_probs`); `pred_text_prob` keeps the path rows, bit for bit
     blk["BEAM_DISTRIBUTIONS"] = False
+    # MI355X build only: "" = off, nothing changes; a regex (the subset of evaluation/pattern.py) = with BEAM_WIDTH >= 1
+    # (ValueError otherwise) the head builds a one-segment, case-sensitive DecodePattern at construction and the search can only
+    # spell strings the regex accepts (RecognizerRCNNHeadV3.set_pattern, glass_beam_search_dfa)
+    blk["DECODE_PATTERN"] = ""
     cfg.MODEL.merge_from_other_cfg({"ROI_RECOGNIZER_HEAD": blk})
 
 

@@ -6,7 +6,8 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 
 def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[[Dict], Dict], writer=None,
-                         batch_size: int = 8, lexicon=None, lexicon_key: Optional[Callable[[Dict], object]] = None) -> List[Dict]:
+                         batch_size: int = 8, lexicon=None, lexicon_key: Optional[Callable[[Dict], object]] = None, pattern=None,
+                         pattern_key: Optional[Callable[[Dict], object]] = None) -> List[Dict]:
     """Run `model` over `dataset_dicts` and return its per-image outputs in input order.
 
     The reference evaluates one image per call.  Here up to `batch_size` images share a call, grouped by their own padded
@@ -19,26 +20,43 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
     (`RecognizerRCNNHeadV3.set_lexicon`, which needs BEAM_WIDTH >= 1) for the run and back to what it had afterwards; every
     word the model emits is then a word of the lexicon.  `lexicon_key` (mapped input -> key of a dict lexicon, e.g. the
     image id of the per-image strong lexicons): the segments of a call's images are set right before the call; without it
-    every image decodes against segment 0."""
+    every image decodes against segment 0.
+
+    `pattern` (evaluation.pattern.DecodePattern) / `pattern_key`: the same for pattern-constrained decoding
+    (`RecognizerRCNNHeadV3.set_pattern`); a pattern the head had before (MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN) is put back
+    afterwards.  Not together with `lexicon`."""
     assert batch_size >= 1
     if lexicon is None and lexicon_key is not None:
         raise ValueError("lexicon_key without a lexicon")
+    if pattern is None and pattern_key is not None:
+        raise ValueError("pattern_key without a pattern")
+    if lexicon is not None and pattern is not None:
+        raise ValueError("lexicon and pattern together")
     head = None
-    if lexicon is not None:
+    if lexicon is not None or pattern is not None:
         import torch
         from ..ops import native
         head = model.roi_heads.recognizer_head
-        before = (head.lexicon, head.image_segments)
-        head.set_lexicon(lexicon)
+        before = (head.lexicon, head.pattern, head.image_segments)
+        head.lexicon = head.pattern = head.image_segments = None
+        try:
+            if lexicon is not None:
+                head.set_lexicon(lexicon)
+            else:
+                head.set_pattern(pattern)
+        except Exception:
+            head.lexicon, head.pattern, head.image_segments = before
+            raise
+    table, table_key = (lexicon, lexicon_key) if lexicon is not None else (pattern, pattern_key)
     d = model.backbone.size_divisibility
     outputs: List[Optional[Dict]] = [None] * len(dataset_dicts)
     pending: Dict[tuple, List[tuple]] = {}
 
     def run(group: List[tuple]) -> None:
         inputs = [inp for _, inp in group]
-        if lexicon_key is not None:
-            segments = [lexicon.segment(lexicon_key(inp)) for inp in inputs]
-            head.image_segments = native.upload(segments, torch.int32, lexicon.device)
+        if table_key is not None:
+            segments = [table.segment(table_key(inp)) for inp in inputs]
+            head.image_segments = native.upload(segments, torch.int32, table.device)
         outs = list(model(inputs))
         assert len(outs) == len(inputs)
         if writer is not None:
@@ -59,5 +77,5 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
             run(group)
     finally:
         if head is not None:
-            head.lexicon, head.image_segments = before
+            head.lexicon, head.pattern, head.image_segments = before
     return outputs

@@ -13,6 +13,8 @@
   * `LexiconTrie` - the same lexicons as a trie over the decoder's classes, for the OTHER lexicon protocol: decoding that can
     only emit lexicon words (glass_beam_search_lexicon, `ASTER_V2.beam_decode(lexicon=...)`,
     `RecognizerRCNNHeadV3.set_lexicon`), where the matchers above repair a word after it was decoded.
+    evaluation/pattern.py generalises it: `DecodePattern` is any finite automaton over the same fold symbols (a regex, a
+    character set, or this trie through `DecodePattern.from_trie`).
 
 Symbols: both sides are upper-cased with `str.upper()` as the reference does (once, at load, for the lexicon: it can
 change a word's length, e.g. 'ß' -> 'SS').  Queries are ASCII (the writer strips other characters first, `de_ascii`);

@@ -161,7 +161,8 @@ class GlassRunner:
                                       "(pred_mask_rois / pred_mask_boxes) instead")
         if getattr(getattr(heads, "recognizer_head", None), "image_segments", None) is not None:
             raise NotImplementedError("run_tiled: the recogniser head carries per-image lexicon segments (image_segments); the "
-                                      "views of a tiled image are not images of that list - set the lexicon with one segment")
+                                      "views of a tiled image are not images of that list - set the lexicon with one segment "
+                                      "(the same holds for a pattern's segments)")
         height, width = image.shape[:2]
         scale = float(scale)
         if not (scale > 0 and np.isfinite(scale)):

@@ -22,6 +22,10 @@ log-likelihood of a transcription; `ASTER_V2.forward(features, labels)` is the r
 Lexicon-constrained decoding: `beam_decode(..., lexicon=LexiconTrie, segments=...)` is the search restricted to the words of
 a lexicon (glass_beam_search_lexicon, include/glass_hip_ext.h; the reference has no counterpart): the k most likely lexicon
 words under the model, with their log-likelihoods.
+
+Pattern-constrained decoding: `beam_decode(..., pattern=DecodePattern, segments=...)` is the same search with the trie
+generalised to a finite automaton over the same fold symbols (glass_beam_search_dfa, include/glass_hip_feature_dfa.h;
+evaluation/pattern.py compiles a regex, a character set or a trie): the k most likely strings the pattern accepts.
 """
 from __future__ import annotations
 
@@ -50,7 +54,8 @@ class BeamResult(_BeamFields):
     (code that unpacks a result or rebuilds one from its fields is unaffected); `distributions` rides as an attribute:
     float32 full per-step rows, [B, L, C] ("best") / [B, k, L, C] ("all"), default None.  So does `words` of a
     lexicon-constrained search: int32 [B, k], the lexicon word of every hypothesis (index into `LexiconTrie.upper`), -1
-    where there is none; default None."""
+    where there is none; default None.  A pattern-constrained search puts its tags there: the word index for a pattern built
+    with `DecodePattern.from_trie`, 0 for a regex, -1 where there is no hypothesis."""
 
     def __new__(cls, symbols, scores, lengths, path_probs=None, distributions=None, words=None):
         self = super().__new__(cls, symbols, scores, lengths, path_probs)
@@ -223,18 +228,18 @@ class ASTER_V2(InferenceModule):
             out = tuple(o.squeeze(1) if o is not None else None for o in out)
         return ForcedResult(*out)
 
-    def _lexicon_segments(self, trie, segments, B: int, eos: int, device) -> torch.Tensor:
-        """the checks of `beam_decode(lexicon=trie, segments=...)` -> item segments int32 [B] on the device.  Host-given
-        segments are checked before they are uploaded; a device tensor is passed through unread (the kernel gives an item
-        whose segment is out of range no hypothesis)."""
+    def _lexicon_segments(self, trie, segments, B: int, eos: int, device, what: str = "lexicon trie") -> torch.Tensor:
+        """the checks of `beam_decode(lexicon=trie, segments=...)` (and of `pattern=`, `what` = "pattern") -> item segments
+        int32 [B] on the device.  Host-given segments are checked before they are uploaded; a device tensor is passed through
+        unread (the kernel gives an item whose segment is out of range no hypothesis)."""
         for name, have, want in (("classes", trie.num_classes, self.num_classes), ("max_len", trie.max_len, self.max_word_len),
                                  ("eos", trie.eos, int(eos))):
             if have != want:
-                raise ValueError(f"beam_decode: the lexicon trie was built for {name} = {have}, the decoder has {want}")
+                raise ValueError(f"beam_decode: the {what} was built for {name} = {have}, the decoder has {want}")
         S = len(trie.keys)
         if segments is None:
             if S != 1:
-                raise ValueError(f"beam_decode: segments=None needs a one-segment lexicon (this one has {S})")
+                raise ValueError(f"beam_decode: segments=None needs a one-segment {what.split()[0]} (this one has {S})")
             return torch.zeros((B,), dtype=torch.int32, device=device)
         if torch.is_tensor(segments) and segments.device.type != "cpu":
             if segments.dtype != torch.int32 or tuple(segments.shape) != (B,):
@@ -250,7 +255,7 @@ class ASTER_V2(InferenceModule):
         return K.upload(seg.contiguous(), torch.int32, device)
 
     def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False,
-                    distributions: Optional[str] = None, lexicon=None, segments=None) -> "BeamResult":
+                    distributions: Optional[str] = None, lexicon=None, segments=None, pattern=None) -> "BeamResult":
         """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
         synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
         `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
@@ -266,17 +271,29 @@ class ASTER_V2(InferenceModule):
         carries `.words` int32 [B,k] (index into `lexicon.upper`; two case variants of a word are two hypotheses with one
         index).  With fewer than k words the rest have score -inf, length 0, word -1.  `segments`: int32 [B] on the device,
         a host sequence of segment numbers (checked here), or None = all 0 (a one-segment lexicon only).  ValueError if the
-        trie was built for another number of classes, max_len or eos."""
+        trie was built for another number of classes, max_len or eos.
+        `pattern` (evaluation.pattern.DecodePattern; not together with `lexicon`): the search can only spell strings the
+        pattern accepts (glass_beam_search_dfa) - the k most likely of them, complete ones only, at most max_word_len - 1
+        characters; `segments` and the checks as for a lexicon, and `.words` carries the tags: the word index for
+        `DecodePattern.from_trie`, 0 for a regex, -1 for an absent hypothesis (score -inf, length 0)."""
         if distributions not in (None, "best", "all"):
             raise ValueError(f'beam_decode: distributions must be None, "best" or "all" (got {distributions!r})')
-        if lexicon is None and segments is not None:
+        if lexicon is not None and pattern is not None:
+            raise ValueError("beam_decode: lexicon and pattern together (DecodePattern.from_trie turns a lexicon into a pattern)")
+        if lexicon is None and pattern is None and segments is not None:
             raise ValueError("beam_decode: segments without a lexicon")
         x = x.contiguous()
         B, T, D = x.shape
         seg = self._lexicon_segments(lexicon, segments, B, eos, x.device) if lexicon is not None else None
+        if pattern is not None:
+            seg = self._lexicon_segments(pattern, segments, B, eos, x.device, what="pattern")
         xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x      # empty batch: empty results
         words = None
-        if lexicon is not None:
+        if pattern is not None:
+            out = K.beam_search_dfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
+                                    pattern.tensors, seg, path_probs=path_probs)
+            words, out = out[3], out[:3] + out[4:]
+        elif lexicon is not None:
             out = K.beam_search_lexicon(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
                                         lexicon.tensors, seg, path_probs=path_probs)
             words, out = out[3], out[:3] + out[4:]

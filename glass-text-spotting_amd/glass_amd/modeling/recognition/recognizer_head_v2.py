@@ -47,6 +47,16 @@ class RecognizerRCNNHeadV3(InferenceModule):
         if self.beam_distributions and self.beam_width < 1:
             raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.BEAM_DISTRIBUTIONS needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 "
                              f"(got BEAM_WIDTH {self.beam_width}): the greedy decoder's pred_text_prob already holds full rows")
+        # MI355X build only: a non-empty regex constrains the search to it from construction on (set_pattern with a
+        # one-segment, case-sensitive evaluation.pattern.DecodePattern)
+        regex = str(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "DECODE_PATTERN", "") or "")
+        if regex:
+            if self.beam_width < 1:
+                raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 "
+                                 f"(got BEAM_WIDTH {self.beam_width}): the greedy decoder does not search")
+            from ...evaluation.pattern import DecodePattern
+            self.set_pattern(DecodePattern(regex, self.text_encoder, self.decoder.max_word_len, self.beam_eos,
+                                           device=cfg.MODEL.DEVICE))
 
     def import_weights(self, sd, device, prefix: str) -> None:
         self.backbone.import_weights(sd, device, prefix + "backbone.")
@@ -63,8 +73,13 @@ class RecognizerRCNNHeadV3(InferenceModule):
         `image_segments`: int32 [num_images] on the device (default: segment 0 for every image); it is gathered by the
         RoIs' image ids on the device.  ValueError unless BEAM_WIDTH >= 1, and if the trie does not fit the decoder."""
         if trie is None:
-            self.lexicon = self.image_segments = None
+            self.lexicon = None
+            if self.pattern is None:            # (a pattern's segments are its own)
+                self.image_segments = None
             return
+        if self.pattern is not None:
+            raise ValueError("set_lexicon: a pattern is set (set_pattern(None) first; DecodePattern.from_trie turns a lexicon "
+                             "into a pattern)")
         if self.beam_width < 1:
             raise ValueError(f"set_lexicon needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 (got {self.beam_width}): the greedy "
                              "decoder does not search")
@@ -77,6 +92,31 @@ class RecognizerRCNNHeadV3(InferenceModule):
                     or image_segments.dim() != 1):
                 raise ValueError("set_lexicon: image_segments must be an int32 [num_images] tensor on the device")
         self.lexicon, self.image_segments = trie, image_segments
+
+    pattern = None            # set_pattern: the DecodePattern the search is constrained to (image_segments: its segments)
+
+    def set_pattern(self, pattern, image_segments=None) -> None:
+        """Constrain the decoding to a pattern (evaluation.pattern.DecodePattern; None switches it off): every RoI decodes to
+        the most likely string its image's segment accepts (glass_beam_search_dfa), handed on as path rows exactly as the
+        unconstrained search's - a RoI with no hypothesis gets all-zero rows.  `image_segments` as in set_lexicon.
+        ValueError unless BEAM_WIDTH >= 1, if the pattern does not fit the decoder, and while a lexicon is set."""
+        if pattern is None:
+            self.pattern = self.image_segments = None
+            return
+        if self.lexicon is not None:
+            raise ValueError("set_pattern: a lexicon is set (set_lexicon(None) first)")
+        if self.beam_width < 1:
+            raise ValueError(f"set_pattern needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 (got {self.beam_width}): the greedy "
+                             "decoder does not search")
+        for name, have, want in (("classes", pattern.num_classes, self.decoder.num_classes),
+                                 ("max_len", pattern.max_len, self.decoder.max_word_len), ("eos", pattern.eos, self.beam_eos)):
+            if have != want:
+                raise ValueError(f"set_pattern: the pattern was built for {name} = {have}, the head has {want}")
+        if image_segments is not None:
+            if (not torch.is_tensor(image_segments) or image_segments.device.type == "cpu" or image_segments.dtype != torch.int32
+                    or image_segments.dim() != 1):
+                raise ValueError("set_pattern: image_segments must be an int32 [num_images] tensor on the device")
+        self.pattern, self.image_segments = pattern, image_segments
 
     def _roi_segments(self, roi_image: torch.Tensor, num_images: int) -> torch.Tensor:
         if self.image_segments is None:
@@ -106,6 +146,8 @@ class RecognizerRCNNHeadV3(InferenceModule):
             enc = self.encoder.forward_nhwc(f, rnn=rnn, status=status)
             if self.beam_width > 0:         # the search has no in-kernel hand-off: only the encoder is guarded
                 lex = {} if self.lexicon is None else {"lexicon": self.lexicon, "segments": self._roi_segments(roi_image, num_images)}
+                if self.pattern is not None:
+                    lex = {"pattern": self.pattern, "segments": self._roi_segments(roi_image, num_images)}
                 if self.beam_distributions:
                     r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best", **lex)
                     return r.path_probs, r.distributions

@@ -1455,6 +1455,51 @@ def beam_search_lexicon(x: torch.Tensor, xproj: torch.Tensor, weights: dict, bea
     return (symbols, scores, lengths, words, path) if path_probs else (symbols, scores, lengths, words)
 
 
+def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
+                    eos: int, dfa: dict, item_pattern: torch.Tensor, path_probs: bool = False):
+    """the beam search constrained by an automaton (glass_beam_search_dfa): as `beam_search_lexicon`, with `dfa` - the device
+    tensors next int32 [N,F] (target | min(dist, 127) << 24, or -1), accept int32 [N], start int32 [S], fold int32 [C] and the
+    int F (evaluation.pattern.DecodePattern.tensors) - in the place of the trie, and item_pattern int32 [B] (the segment of
+    every item) on x's device -> (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k], tags int32 [B,k][, path rows
+    [B,max_len,C]]): the k most likely strings of each item's segment, best first; tags = `accept` of the terminal state.
+    No host synchronisation; limits are checked by the library."""
+    B, T, D, dev = _search_inputs("beam_search_dfa", x, xproj)
+    k, C, L = int(beam_width), int(num_classes), int(max_len)
+    F = int(dfa["F"])
+    arrays = {n: dfa.get(n) for n in ("next", "accept", "start", "fold")}
+    N = S = 0
+    for n, t in arrays.items():
+        if t is None:
+            continue
+        _i32(t, n)
+        if t.device != dev:
+            raise GlassLibraryError(f"beam_search_dfa: {n} on {t.device}, x on {dev}")
+    if arrays["next"] is not None:
+        nx = arrays["next"]
+        N = int(nx.shape[0])
+        if nx.dim() != 2 or (1 <= F <= 256 and nx.shape[1] != F):       # (an F outside 1..256 is the library's to refuse)
+            raise GlassLibraryError(f"beam_search_dfa: next {tuple(nx.shape)} is not [N, F={F}]")
+        if arrays["accept"] is not None and tuple(arrays["accept"].shape) != (N,):
+            raise GlassLibraryError(f"beam_search_dfa: accept {tuple(arrays['accept'].shape)} is not [N={N}]")
+    if arrays["start"] is not None:
+        S = int(arrays["start"].numel())
+    if arrays["fold"] is not None and tuple(arrays["fold"].shape) != (C,):
+        raise GlassLibraryError(f"beam_search_dfa: fold {tuple(arrays['fold'].shape)} is not [C={C}]")
+    _i32(item_pattern, "item_pattern")
+    if tuple(item_pattern.shape) != (B,) or item_pattern.device != dev:
+        raise GlassLibraryError(f"beam_search_dfa: item_pattern {tuple(item_pattern.shape)} on {item_pattern.device} is not [B={B}] on {dev}")
+    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
+    tags = torch.empty_like(lengths)
+    w = _decoder_weights(weights)
+    nbytes = int(lib().glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, L))
+    ws = _workspace(nbytes, dev)
+    check(lib().glass_beam_search_dfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _opt(arrays["next"]),
+                                      _opt(arrays["accept"]), _opt(arrays["start"]), _opt(arrays["fold"]), N, S, F,
+                                      _opt(item_pattern), _dev(symbols), _dev(scores), _dev(lengths), _dev(tags), _opt(path),
+                                      _dev(ws), nbytes, stream_handle()), "glass_beam_search_dfa")
+    return (symbols, scores, lengths, tags, path) if path_probs else (symbols, scores, lengths, tags)
+
+
 def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: torch.Tensor, lengths: Optional[torch.Tensor],
                   num_classes: int, max_len: int, eos: int, probs: bool = False, logits: bool = False):
     """the decoder with the emitted symbols given (glass_forced_decode; reference AttentionRecognitionHead.forward): x, xproj
