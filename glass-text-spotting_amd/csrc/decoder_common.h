@@ -1,5 +1,5 @@
 // Shared by the attention-GRU decoder (decoder.hip: the greedy decode and the single step) and its searches
-// (decoder_search.hip: beam search, forced decoding, the lexicon- and pattern-constrained beam searches): limits, the kernel
+// (decoder_search.hip: beam search, forced decoding, the lexicon-, pattern- and weighted-pattern-constrained beam searches): limits, the kernel
 // parameter block, the host helpers every entry point uses, and the pieces of one decoder step on the rows of ONE item.
 #pragma once
 #include "recognition_common.h"
@@ -103,6 +103,45 @@ __device__ __forceinline__ void rows_topk(int k, int C, int u, int lane, int wav
       for (int r = 0; r < KB; ++r) {
         if (r < k && !((taken >> r) & 1u)) {
           const float v = ((allow >> r) & 1u) ? cand[r][u] : -INFINITY;
+          if (besti == 0x7fffffff || v > best) { best = v; besti = r * C + u; }
+        }
+      }
+    }
+    wave_argmax_first(best, besti);
+    if (lane == 0) { wbest[j & 1][wave] = best; wbesti[j & 1][wave] = besti; }
+    __syncthreads();
+    float gb = wbest[j & 1][0];
+    int gi = wbesti[j & 1][0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const float vb = wbest[j & 1][w];
+      const int vi = wbesti[j & 1][w];
+      if (vi != 0x7fffffff && (gi == 0x7fffffff || vb > gb || (vb == gb && vi < gi))) { gb = vb; gi = vi; }
+    }
+    // k <= C: a candidate is always left and gi is a real index - unless the logits hold NaN (outside the contract):
+    // the tables must still hold valid slots and classes, they index memory in the later steps and in the finalisation
+    if (gi == 0x7fffffff) gi = j;
+    const int beam = gi / C, cls = gi - beam * C;
+    if (u == cls) taken |= 1u << beam;
+    if (u == 0) emit(j, gb, beam, cls);
+  }
+}
+
+// rows_topk with the candidate's score from a callback: value(r) = thread u's score of (beam r, class u), asked only where the
+// bit is set and u < C (the weighted search: cand[r][u] fused with the thread's weight term of beam r).  The same rounds, rule
+// and emit; a copy, so that the kernels of the unweighted searches are the code they were.
+template <int KB, class Value, class Emit>
+__device__ __forceinline__ void rows_topk_by(int k, int C, int u, int lane, int wave, unsigned allow, Value value,
+                                             float (&wbest)[2][4], int (&wbesti)[2][4], Emit emit) {
+  unsigned taken = 0u;
+  for (int j = 0; j < k; ++j) {
+    float best = -INFINITY;
+    int besti = 0x7fffffff;
+    if (u < C) {
+#pragma unroll
+      for (int r = 0; r < KB; ++r) {
+        if (r < k && !((taken >> r) & 1u)) {
+          const float v = ((allow >> r) & 1u) ? value(r) : -INFINITY;
           if (besti == 0x7fffffff || v > best) { best = v; besti = r * C + u; }
         }
       }

@@ -1,10 +1,11 @@
 // Searches over the attention-GRU decoder of decoder.hip, each behind one ABI call with no host synchronisation: beam search,
-// forced decoding (the symbols given) and the constrained beam searches (a lexicon trie, or any DFA).  Per step they run the decoder's GRU launch
+// forced decoding (the symbols given) and the constrained beam searches (a lexicon trie, any DFA, or a weighted DFA).  Per step they run the decoder's GRU launch
 // (dec_gru_step) on all rows and one step kernel, one workgroup per item, composed of the rows_* pieces of decoder_common.h.
 #include <type_traits>
 #include "decoder_common.h"
 #include "glass_hip_ext.h"
 #include "glass_hip_feature_dfa.h"
+#include "glass_hip_feature_wdfa.h"
 
 // ================================================================== beam search (AttentionRecognitionHead.beam_search)
 // The whole search of reference prediction_aster.py:101-222 behind one ABI call: per step dec_gru_kernel on the B*k state rows
@@ -393,6 +394,7 @@ struct LexParams {
   const int* item_segment;          // [B]
   int* nd;                          // workspace [B][L][k]
   int N, S, F, MW;
+  static constexpr bool weighted = false;
   // ---- what con_step_kernel asks of a constraint (DfaParams answers the same questions from its table)
   // the node of an item's first beam; the caller checks it against N
   __device__ __forceinline__ int root(int b) const {
@@ -428,6 +430,7 @@ struct DfaParams {
   const int* item_segment;          // [B]
   int* nd;                          // workspace [B][L][k]
   int N, S, F;
+  static constexpr bool weighted = false;
   __device__ __forceinline__ int root(int b) const {
     const int seg = item_segment[b];
     return (seg >= 0 && seg < S) ? start[seg] : -1;
@@ -450,7 +453,60 @@ struct DfaParams {
   }
 };
 
-// beam_step_kernel with the mask of a constraint CP (LexParams: the trie, DfaParams: the automaton).  Thread u owns class u:
+// The constraint of glass_beam_search_wdfa (glass_hip_feature_wdfa.h): DfaParams with a weight on every transition, stop and
+// start.  `weighted` switches con_step_kernel to two scores per slot: the model score (bp.sc, the arithmetic of the other
+// searches) and the weight sum (wa); the beams are ranked by fuse(model score, weight sum) (fu).
+struct WdfaParams {
+  const unsigned long long* trans;  // [N][F]: next as in DfaParams in the low half, the float weight in the high half: read as
+                                    // ONE 64-bit integer (two ints of a struct or an int2 become two dependent 32-bit loads)
+  const float* final_w;             // [N]
+  const float* start_w;             // [S]
+  const int* accept;                // [N]
+  const int* start;                 // [S]
+  const int* fold;                  // [C]
+  const int* item_segment;          // [B]
+  int* nd;                          // workspace [B][L][k]
+  float* wa;                        // workspace [B][L][k]: the slot's weight sum after the step
+  float* fu;                        // workspace [B][L][k]: the slot's fused score after the step
+  float scale;
+  int N, S, F;
+  static constexpr bool weighted = true;
+  __device__ __forceinline__ int root(int b) const {
+    const int seg = item_segment[b];
+    return (seg >= 0 && seg < S) ? start[seg] : -1;
+  }
+  // the weight sum an item starts with (root(b) has checked the segment)
+  __device__ __forceinline__ float root_weight(int b) const { return start_w[item_segment[b]]; }
+  // ONE rounding: the product is not rounded on its own (scale = 0 or a = 0 give m bit for bit)
+  __device__ __forceinline__ float fuse(float m, float a) const { return __fmaf_rn(scale, a, m); }
+  // allow_bit of DfaParams with the weight: `a` = the beam's weight sum -> `term` = the candidate's; one 64-bit load decides a
+  // symbol and weighs it.  A weight (or a sum) that is not finite: the candidate is absent.
+  __device__ __forceinline__ unsigned allow_term(bool stop, bool sym, int f, int node, int step, int L, float a, float& term) const {
+    bool ok = false;
+    float w = 0.f;
+    if (stop) {
+      ok = step >= 1 && accept[node] >= 0;
+      w = final_w[node];
+    } else if (sym) {
+      const unsigned long long e = trans[(long)node * F + f];
+      const int nx = (int)(unsigned)e;
+      ok = nx >= 0 && step + 1 + (nx >> 24) <= L - 1;
+      w = __uint_as_float((unsigned)(e >> 32));
+    }
+    term = a + w;
+    return (ok && fabsf(term) < INFINITY) ? 1u : 0u;
+  }
+  // follow of DfaParams, and the weight of the transition
+  __device__ __forceinline__ int follow(int par, int f, float& w) const {
+    const unsigned long long e = trans[(long)par * F + f];
+    const int nx = (int)(unsigned)e, q = nx & 0xffffff;
+    w = __uint_as_float((unsigned)(e >> 32));
+    return (nx >= 0 && q < N) ? q : -1;
+  }
+};
+
+// beam_step_kernel with the mask of a constraint CP (LexParams: the trie, DfaParams: the automaton, WdfaParams: the weighted
+// automaton, whose extra work is all under `if constexpr (CP::weighted)`: the other two kernels are what they were).  Thread u owns class u:
 // its k mask words or table entries (one per beam) are loaded once per step into the bit set `allow`; the k node ids live in
 // LDS.  After the selection, thread j moves slot j to its child node / target state.
 template <int KB, class CP>
@@ -461,6 +517,7 @@ __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams b
   __shared__ float cand[KB][DEC_CMAX];
   __shared__ float energy[KB][DEC_TMAX];
   __shared__ float run[KB], ssel[KB];
+  __shared__ float arun[KB];                                            // weighted only: the slots' weight sums
   __shared__ int ysel[KB], psel[KB], snode[KB];
   __shared__ float wbest[2][4];
   __shared__ int wbesti[2][4];
@@ -473,60 +530,116 @@ __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams b
     psel[u] = 0;
     ssel[u] = -INFINITY;
     float rs = -INFINITY;
+    float ws = 0.f;
     int node = -1;
     if (u < k) {
       if (step <= 0) {
         if (u == 0) {
           rs = 0.f;
           node = lp.root(b);
+          if constexpr (CP::weighted) {
+            if (node >= 0) ws = lp.root_weight(b);
+          }
         }
       } else {
         const long i = ((long)b * L + (step - 1)) * k + u;
         rs = bp.sc[i];
         node = bp.sy[i] == bp.eos ? -1 : lp.nd[i];
+        if constexpr (CP::weighted) ws = lp.wa[i];
+      }
+      if constexpr (CP::weighted) {
+        if (!(fabsf(ws) < INFINITY)) node = -1;                         // nothing is ranked by a weight that is not finite
       }
       if (node < 0 || node >= lp.N) { node = -1; rs = -INFINITY; }      // a dead slot: no node, never finite again
     }
     run[u] = rs;
     snode[u] = node;
+    if constexpr (CP::weighted) arun[u] = node >= 0 ? ws : 0.f;
   }
   __syncthreads();
   if (step >= 0) {
     // ---- the mask of class u against the k nodes: bit r of `allow` = candidate (beam r, class u) may be emitted
+    // (weighted: term[r] = the weight sum of that candidate, next to its bit)
     unsigned allow = 0u;
-    if (u < C) {
-      const bool stop = u == bp.eos;
-      const int f = lp.fold[u];
-      const bool sym = !stop && f >= 0 && f < lp.F;
+    float term[CP::weighted ? KB : 1];
+    if constexpr (CP::weighted) {
 #pragma unroll
-      for (int r = 0; r < KB; ++r) {
-        const int node = r < k ? snode[r] : -1;
-        if (node >= 0) allow |= lp.allow_bit(stop, sym, f, node, step, L) << r;
+      for (int r = 0; r < KB; ++r) term[r] = 0.f;
+    }
+    if constexpr (!CP::weighted) {
+      if (u < C) {
+        const bool stop = u == bp.eos;
+        const int f = lp.fold[u];
+        const bool sym = !stop && f >= 0 && f < lp.F;
+#pragma unroll
+        for (int r = 0; r < KB; ++r) {
+          const int node = r < k ? snode[r] : -1;
+          if (node >= 0) allow |= lp.allow_bit(stop, sym, f, node, step, L) << r;
+        }
       }
     }
     rows_fc<KB>(p, C, u, h, cand);
+    if constexpr (CP::weighted) {
+      // after the mat-vec, not before it as the masks above: k weight terms alive across it cost the KB = 8 and 16 kernels 8
+      // VGPRs (171 / 170 instead of 163 / 162) and with them a wave per SIMD; the loads still overlap the log-softmax
+      if (u < C) {
+        const bool stop = u == bp.eos;
+        const int f = lp.fold[u];
+        const bool sym = !stop && f >= 0 && f < lp.F;
+#pragma unroll
+        for (int r = 0; r < KB; ++r) {
+          const int node = r < k ? snode[r] : -1;
+          if (node >= 0) allow |= lp.allow_term(stop, sym, f, node, step, L, arun[r], term[r]) << r;
+        }
+      }
+    }
     __syncthreads();
     rows_score<KB>(k, C, lane, wave, run, cand);
     __syncthreads();
-    rows_topk<KB>(k, C, u, lane, wave, allow, cand, wbest, wbesti, [&](int j, float score, int beam, int cls) {
-      const long i = ((long)b * L + step) * k + j;
-      bp.sc[i] = score; bp.pr[i] = beam; bp.sy[i] = cls;
-      ysel[j] = cls; psel[j] = beam; ssel[j] = score;
-    });
+    if constexpr (CP::weighted) {
+      // cand stays the model candidates; the top-k ranks them fused with the thread's k weight terms
+      rows_topk_by<KB>(k, C, u, lane, wave, allow, [&](int r) { return lp.fuse(cand[r][u], term[r]); }, wbest, wbesti,
+                       [&](int j, float score, int beam, int cls) {
+        const long i = ((long)b * L + step) * k + j;
+        lp.fu[i] = score; bp.pr[i] = beam; bp.sy[i] = cls;
+        ysel[j] = cls; psel[j] = beam; ssel[j] = score;
+      });
+    } else {
+      rows_topk<KB>(k, C, u, lane, wave, allow, cand, wbest, wbesti, [&](int j, float score, int beam, int cls) {
+        const long i = ((long)b * L + step) * k + j;
+        bp.sc[i] = score; bp.pr[i] = beam; bp.sy[i] = cls;
+        ysel[j] = cls; psel[j] = beam; ssel[j] = score;
+      });
+    }
     __syncthreads();
     // ---- slot j follows its symbol into the trie / automaton: the child node, the node itself for <eos> (the terminal node,
     // whose word the finalisation reports), no node for a selected -inf candidate or an index outside the arrays
+    // (weighted: the slot's two scores too - the winner's exact model score from cand, and its weight sum by the addition the
+    // candidate was ranked with, on the entry loaded once more)
     if (u < k) {
       const int cls = ysel[u], par = snode[psel[u]];
       int node = -1;
+      float w = 0.f;
       if (ssel[u] > -INFINITY && par >= 0) {
-        if (cls == bp.eos) node = par;
-        else {
+        if (cls == bp.eos) {
+          node = par;
+          if constexpr (CP::weighted) w = lp.final_w[par];
+        } else {
           const int f = lp.fold[cls];
-          if (f >= 0 && f < lp.F) node = lp.follow(par, f);
+          if constexpr (CP::weighted) {
+            if (f >= 0 && f < lp.F) node = lp.follow(par, f, w);
+          } else {
+            if (f >= 0 && f < lp.F) node = lp.follow(par, f);
+          }
         }
       }
-      lp.nd[((long)b * L + step) * k + u] = node;
+      const long i = ((long)b * L + step) * k + u;
+      lp.nd[i] = node;
+      if constexpr (CP::weighted) {
+        const bool fin = ssel[u] > -INFINITY && par >= 0;
+        bp.sc[i] = fin ? cand[psel[u]][cls] : -INFINITY;
+        lp.wa[i] = fin ? arun[psel[u]] + w : 0.f;
+      }
     }
     if (step + 1 >= L) return;
     __syncthreads();
@@ -538,10 +651,15 @@ __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams b
 // The k best completed entries of one item, one wavefront per item: an entry (t, slot) is completed when its symbol is <eos>
 // and its score finite; order = score descending, then flat index t*k + slot ascending (t, then slot).  Lane l owns the
 // entries l + 64 i; k rounds of the wavefront arg-max, then lane r walks result r back through the predecessor table.
+// W (the weighted search): the entries are ranked by their fused scores `fused` [B][L][k], which go to out_sc; the model scores
+// (bp.sc) go to out_model and, as without W, make the path rows.
+template <bool W>
 __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams lp, int C, int* __restrict__ out_sym,
                                                        float* __restrict__ out_sc, int* __restrict__ out_len,
-                                                       int* __restrict__ out_word, float* __restrict__ out_path) {
+                                                       int* __restrict__ out_word, float* __restrict__ out_path,
+                                                       const float* __restrict__ fused, float* __restrict__ out_model) {
   __shared__ float sc[BEAM_LMAX * BEAM_KMAX];
+  __shared__ float fu[W ? BEAM_LMAX * BEAM_KMAX : 1];
   __shared__ int pr[BEAM_LMAX * BEAM_KMAX], sy[BEAM_LMAX * BEAM_KMAX], nd[BEAM_LMAX * BEAM_KMAX];
   __shared__ int res[BEAM_KMAX];
   __shared__ int p_idx[BEAM_LMAX];            // the slots of result 0 along its ancestor chain
@@ -551,6 +669,7 @@ __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams 
     pr[i] = bp.pr[(long)b * n + i];
     sy[i] = bp.sy[(long)b * n + i];
     nd[i] = lp.nd[(long)b * n + i];
+    if constexpr (W) fu[i] = fused[(long)b * n + i];
   }
   __syncthreads();
   unsigned taken = 0u;
@@ -561,7 +680,9 @@ __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams 
     for (int i = 0; i < BEAM_LMAX * BEAM_KMAX / 64; ++i) {
       const int e = lane + 64 * i;
       if (e < n && !((taken >> i) & 1u) && sy[e] == bp.eos) {
-        const float v = sc[e];
+        float v;
+        if constexpr (W) v = fu[e];
+        else v = sc[e];
         if (v > -INFINITY && v < INFINITY && (besti == 0x7fffffff || v > best)) { best = v; besti = e; }
       }
     }
@@ -577,13 +698,19 @@ __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams 
     if (e < 0) {
       for (int t = 0; t < L; ++t) os[t] = bp.eos;
       out_sc[row] = -INFINITY;
+      if constexpr (W) out_model[row] = -INFINITY;
       out_len[row] = 0;
       out_word[row] = -1;
     } else {
       const int t0 = e / k;
       int slot = e - t0 * k;
       const int node = nd[e];
-      out_sc[row] = sc[e];
+      if constexpr (W) {
+        out_sc[row] = fu[e];
+        out_model[row] = sc[e];
+      } else {
+        out_sc[row] = sc[e];
+      }
       out_len[row] = t0 + 1;
       out_word[row] = (node >= 0 && node < lp.N) ? lp.node_word[node] : -1;
       for (int t = L - 1; t > t0; --t) os[t] = bp.eos;
@@ -651,8 +778,8 @@ extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, con
     lex_step(step);
   }
   GLASS_CHECK_LAUNCH("glass_beam_search_lexicon");
-  hipLaunchKernelGGL(lex_final_kernel, gb, dim3(64), 0, s, bp, lp, C, out_symbols, out_scores, out_lengths, out_words,
-                     out_path_probs);
+  hipLaunchKernelGGL(lex_final_kernel<false>, gb, dim3(64), 0, s, bp, lp, C, out_symbols, out_scores, out_lengths, out_words,
+                     out_path_probs, (const float*)nullptr, (float*)nullptr);
   GLASS_CHECK_LAUNCH("glass_beam_search_lexicon(final)");
   return GLASS_OK;
 }
@@ -702,7 +829,72 @@ extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const g
     dfa_step(step);
   }
   GLASS_CHECK_LAUNCH("glass_beam_search_dfa");
-  hipLaunchKernelGGL(lex_final_kernel, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags, out_path_probs);
+  hipLaunchKernelGGL(lex_final_kernel<false>, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags,
+                     out_path_probs, (const float*)nullptr, (float*)nullptr);
   GLASS_CHECK_LAUNCH("glass_beam_search_dfa(final)");
+  return GLASS_OK;
+}
+
+// ================================================================== weighted-automaton beam search (glass_hip_feature_wdfa.h)
+// glass_beam_search_dfa with a weight on every transition, stop and start: the same step kernel with WdfaParams as its
+// constraint (two scores per slot, ranked by their fusion), lex_final_kernel<true>.
+//   workspace: that of glass_beam_search_dfa | weight sums [B,L,k] | fused scores [B,L,k]
+extern "C" int64_t glass_beam_search_wdfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
+  return glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len) + (int64_t)2 * B * max_len * k * (int64_t)sizeof(float);
+}
+
+extern "C" int glass_beam_search_wdfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
+                                      int C, int max_len, int eos, const glass_wdfa_transition* trans, const float* final_w,
+                                      const float* start_w, const int* accept, const int* start, const int* fold, int N, int S,
+                                      int F, const int* item_pattern, float weight_scale, int* out_symbols, float* out_scores,
+                                      float* out_model_scores, int* out_lengths, int* out_tags, float* out_path_probs,
+                                      void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
+  static_assert(sizeof(glass_wdfa_transition) == 8 && offsetof(glass_wdfa_transition, w) == 4, "one 64-bit load per table entry");
+  if (int rc = search_limits("glass_beam_search_wdfa", true, B, k, T, D, C, max_len)) return rc;
+  GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256,
+                  "glass_beam_search_wdfa: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", N, S, F);
+  GLASS_CHECK_ARG(weight_scale == weight_scale && weight_scale - weight_scale == 0.f,
+                  "glass_beam_search_wdfa: weight_scale must be finite (got %g)", (double)weight_scale);
+  if (B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_model_scores && out_lengths && out_tags && workspace,
+                  "glass_beam_search_wdfa: null pointer");
+  GLASS_CHECK_ARG(trans && final_w && start_w && accept && start && fold && item_pattern,
+                  "glass_beam_search_wdfa: null automaton array");
+  GLASS_CHECK_ARG((reinterpret_cast<uintptr_t>(trans) & 7u) == 0, "glass_beam_search_wdfa: trans is not 8-byte aligned");
+  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len),
+                  "glass_beam_search_wdfa: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  (long long)glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len));
+  hipStream_t s = (hipStream_t)stream;
+  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
+  const BeamLayout lay = beam_layout(B, k, D, max_len);
+  const BeamParams bp = beam_carve(workspace, lay, k, max_len, eos, p);
+  float *hsel = p.h0, *hraw = p.h1;
+  const size_t table = (size_t)B * max_len * k * sizeof(float);
+  char* ws = static_cast<char*>(workspace);
+  WdfaParams wp;
+  wp.trans = reinterpret_cast<const unsigned long long*>(trans); wp.final_w = final_w; wp.start_w = start_w; wp.accept = accept; wp.start = start;
+  wp.fold = fold; wp.item_segment = item_pattern;
+  wp.nd = reinterpret_cast<int*>(ws + lay.end);
+  wp.wa = reinterpret_cast<float*>(ws + lay.end + table);
+  wp.fu = reinterpret_cast<float*>(ws + lay.end + 2 * table);
+  wp.scale = weight_scale; wp.N = N; wp.S = S; wp.F = F;
+  LexParams fin = {};                                                              // what lex_final_kernel reads: nd, N, node_word
+  fin.nd = wp.nd; fin.N = N; fin.node_word = accept;
+  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("glass_beam_search_wdfa: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  const dim3 gb(B);
+  auto wdfa_step = [&](int step) {
+    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL((con_step_kernel<decltype(kb)::value, WdfaParams>), gb, dim3(256), 0, s, p, bp, wp, hraw, step); });
+  };
+  wdfa_step(-1);                                                                  // attention for step 0
+  for (int step = 0; step < max_len; ++step) {
+    dec_gru_step(p, hsel, hraw, s);
+    wdfa_step(step);
+  }
+  GLASS_CHECK_LAUNCH("glass_beam_search_wdfa");
+  hipLaunchKernelGGL(lex_final_kernel<true>, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags,
+                     out_path_probs, (const float*)wp.fu, out_model_scores);
+  GLASS_CHECK_LAUNCH("glass_beam_search_wdfa(final)");
   return GLASS_OK;
 }

@@ -152,6 +152,10 @@ def add_e2e_config(cfg: CN) -> None:
     # (ValueError otherwise) the head builds a one-segment, case-sensitive DecodePattern at construction and the search can only
     # spell strings the regex accepts (RecognizerRCNNHeadV3.set_pattern, glass_beam_search_dfa)
     blk["DECODE_PATTERN"] = ""
+    # MI355X build only: 0.0 = off, nothing changes; else (with DECODE_PATTERN; ValueError otherwise) a bonus per character, a
+    # natural log, on the pattern's transitions: the search ranks by the model score + the bonus times the characters
+    # (DecodePattern.weighted(length_bonus=...), glass_beam_search_wdfa); the word score stays the model's probability
+    blk["DECODE_LENGTH_BONUS"] = 0.0
     cfg.MODEL.merge_from_other_cfg({"ROI_RECOGNIZER_HEAD": blk})
 
 

@@ -1,6 +1,7 @@
 from .lexicon import (DeviceLexicon, LexiconMatcher, LexiconTrie, WeightedLexiconMatcher, encode_query, encode_word, lexicon_layout,  # noqa: F401
                       fold_table, load_lexicon, symbol_classes, weighted_cost_tables)
 from .pattern import DecodePattern  # noqa: F401
+from .weighted_pattern import CharNgramLM, WeightedPattern  # noqa: F401
 from .text_evaluator import (TextResultWriter, boxes_to_polygons, find_match_word, find_match_word_weighted,  # noqa: F401
                              instances_to_coco_json, levenshtein, weighted_edit_distance, masks_to_polygons, match_transcript, normalize_detection_line, rotated_boxes_to_polygons)
 from .driver import inference_on_dataset  # noqa: F401

@@ -24,7 +24,8 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
 
     `pattern` (evaluation.pattern.DecodePattern) / `pattern_key`: the same for pattern-constrained decoding
     (`RecognizerRCNNHeadV3.set_pattern`); a pattern the head had before (MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN) is put back
-    afterwards.  Not together with `lexicon`."""
+    afterwards.  Not together with `lexicon`.  A `WeightedPattern` (evaluation.weighted_pattern) is taken as it is, with
+    weight_scale 1; the head's own scale is put back with its pattern."""
     assert batch_size >= 1
     if lexicon is None and lexicon_key is not None:
         raise ValueError("lexicon_key without a lexicon")
@@ -37,7 +38,7 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
         import torch
         from ..ops import native
         head = model.roi_heads.recognizer_head
-        before = (head.lexicon, head.pattern, head.image_segments)
+        before = (head.lexicon, head.pattern, head.image_segments, head.weight_scale)
         head.lexicon = head.pattern = head.image_segments = None
         try:
             if lexicon is not None:
@@ -45,7 +46,7 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
             else:
                 head.set_pattern(pattern)
         except Exception:
-            head.lexicon, head.pattern, head.image_segments = before
+            head.lexicon, head.pattern, head.image_segments, head.weight_scale = before
             raise
     table, table_key = (lexicon, lexicon_key) if lexicon is not None else (pattern, pattern_key)
     d = model.backbone.size_divisibility
@@ -77,5 +78,5 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
             run(group)
     finally:
         if head is not None:
-            head.lexicon, head.pattern, head.image_segments = before
+            head.lexicon, head.pattern, head.image_segments, head.weight_scale = before
     return outputs

@@ -361,6 +361,7 @@ class LexiconTrie:
     numpy arrays (nodes in breadth-first order, a node's children contiguous and ordered by fold symbol): `fold` int32 [C],
     `child_mask` uint32 [N,MW], `child_base` int32 [N], `node_word` int32 [N] (-1, or the first word that ends there),
     `seg_root` int32 [S] (-1 = an empty segment); child(node, f) = child_base[node] + popcount(mask bits below f).
+    `word_node` int32 [len(upper)] (host only): the node every word ends at, -1 for a word that was left out.
     `tensors` holds them on the device (the mask as int32 bit patterns) with the int "F"."""
 
     def __init__(self, lexicon: Union[Sequence[str], Dict[object, Sequence[str]]], text_encoder_or_characters, max_len: int,
@@ -384,6 +385,7 @@ class LexiconTrie:
         self.mask_words = MW = (F + 31) // 32
         uppers = [[w.upper() for w in words] for words in lists]
         self.upper = [w for words in uppers for w in words]
+        self.segment_sizes = [len(words) for words in lists]      # words per segment, left-out ones included: `upper` in slices
         folded = uppers if self.case_insensitive else lists
         sym_id = {s: i for i, s in enumerate(self.fold_symbols)}
         self.skipped = {"empty": 0, "too_long": 0, "no_class": 0}
@@ -439,6 +441,9 @@ class LexiconTrie:
         if n >= 2 ** 31:
             raise ValueError(f"lexicon trie of {n} nodes (max 2^31 - 1)")
         self.num_nodes = n
+        # the node every word ends at (indexed as `upper`; -1 for a word that was left out): what a word prior is attached to
+        self.word_node = np.full(len(self.upper), -1, dtype=np.int32)
+        self.word_node[w_idx] = at
         self.child_mask = np.ascontiguousarray(np.concatenate(masks))
         self.child_base = np.concatenate(bases).astype(np.int32)
         self.node_word = np.concatenate(words_at).astype(np.int32)

@@ -24,6 +24,9 @@ hypothesis in state q
     may emit class c iff f = fold[c] >= 0, q' = next[q][f] exists and t + 1 + dist[q'] <= L - 1;
     may emit the stop iff accept[q] >= 0 and t >= 1 (the empty string is never emitted, as with the trie).
 So every live hypothesis can still complete; the language in force is {w in L(regex) : 1 <= |w| <= L - 1}.
+
+`DecodePattern.weighted(lm=..., word_logprior=..., length_bonus=...)` (evaluation/weighted_pattern.py) puts a weight on every
+transition of the automaton - a character n-gram model, word priors, a length bonus - for glass_beam_search_wdfa.
 """
 from __future__ import annotations
 
@@ -412,6 +415,9 @@ class DecodePattern:
       `start` int32 [S]: -1 for a segment whose language is empty at this max_len;  `fold` int32 [C].
     Limits (ValueError): N <= 2^24 - 1, `next` at most `table_cap_bytes`, at most `nfa_cap` Thompson states per regex."""
 
+    word_state = None         # from_trie only: int32 [words], the state every word of the trie ends at (-1: left out)
+    segment_sizes = None      # from_trie only: the words of every segment
+
     def __init__(self, patterns: Union[str, Dict[object, str]], text_encoder_or_characters, max_len: int, eos: int,
                  case_insensitive: bool = False, minimize: bool = True, device=None, *,
                  table_cap_bytes: int = NEXT_TABLE_CAP_BYTES, nfa_cap: int = NFA_STATE_CAP):
@@ -542,7 +548,18 @@ class DecodePattern:
             nxt[a:a + len(mask)] = np.where(bits > 0, trie.child_base[a:a + len(mask), None] + rank, -1)
         self._finish(nxt, trie.node_word.copy(), trie.seg_root.copy(), table_cap_bytes,
                      device if device is not None else trie.device, t0)
+        # what `weighted(word_logprior=...)` attaches a prior to: the state every word of `trie.upper` ends at (-1: left out)
+        self.word_state, self.segment_sizes = trie.word_node.copy(), list(trie.segment_sizes)
         return self
+
+    def weighted(self, lm=None, word_logprior=None, length_bonus: float = 0.0, table_cap_bytes: Optional[int] = None,
+                 device=None) -> "WeightedPattern":
+        """this pattern with a weight (a natural log) on every transition, stop and start, for glass_beam_search_wdfa: a
+        character n-gram model `lm` (CharNgramLM) crossed with the states, word priors `word_logprior` pushed toward the root
+        (a `from_trie` pattern only) and a `length_bonus` per symbol; the three add.  evaluation/weighted_pattern.py has the
+        definitions; ValueError for a weight that is not finite and for an argument that does not fit the pattern."""
+        from .weighted_pattern import WEIGHTED_TABLE_CAP_BYTES as cap, WeightedPattern
+        return WeightedPattern(self, lm, word_logprior, length_bonus, cap if table_cap_bytes is None else table_cap_bytes, device)
 
     # ---- queries
     def __len__(self) -> int:

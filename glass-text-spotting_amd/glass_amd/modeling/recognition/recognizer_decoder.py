@@ -26,6 +26,10 @@ words under the model, with their log-likelihoods.
 Pattern-constrained decoding: `beam_decode(..., pattern=DecodePattern, segments=...)` is the same search with the trie
 generalised to a finite automaton over the same fold symbols (glass_beam_search_dfa, include/glass_hip_feature_dfa.h;
 evaluation/pattern.py compiles a regex, a character set or a trie): the k most likely strings the pattern accepts.
+
+Weighted patterns: with a `WeightedPattern` (evaluation/weighted_pattern.py: a character n-gram model, word priors, a length
+bonus) the same call runs glass_beam_search_wdfa (include/glass_hip_feature_wdfa.h): the beams are ranked by the model score
+plus `weight_scale` times the automaton's weights; the model's own scores and the path rows stay what they were.
 """
 from __future__ import annotations
 
@@ -55,12 +59,15 @@ class BeamResult(_BeamFields):
     float32 full per-step rows, [B, L, C] ("best") / [B, k, L, C] ("all"), default None.  So does `words` of a
     lexicon-constrained search: int32 [B, k], the lexicon word of every hypothesis (index into `LexiconTrie.upper`), -1
     where there is none; default None.  A pattern-constrained search puts its tags there: the word index for a pattern built
-    with `DecodePattern.from_trie`, 0 for a regex, -1 where there is no hypothesis."""
+    with `DecodePattern.from_trie`, 0 for a regex, -1 where there is no hypothesis.  With a `WeightedPattern` `scores` are
+    the FUSED scores the search ranked by, and `model_scores` rides as an attribute: float32 [B, k], the model's own sums of
+    log-probabilities (what `path_probs` is made from); default None."""
 
-    def __new__(cls, symbols, scores, lengths, path_probs=None, distributions=None, words=None):
+    def __new__(cls, symbols, scores, lengths, path_probs=None, distributions=None, words=None, model_scores=None):
         self = super().__new__(cls, symbols, scores, lengths, path_probs)
         self.distributions = distributions
         self.words = words
+        self.model_scores = model_scores
         return self
 
 
@@ -255,7 +262,8 @@ class ASTER_V2(InferenceModule):
         return K.upload(seg.contiguous(), torch.int32, device)
 
     def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False,
-                    distributions: Optional[str] = None, lexicon=None, segments=None, pattern=None) -> "BeamResult":
+                    distributions: Optional[str] = None, lexicon=None, segments=None, pattern=None,
+                    weight_scale: float = 1.0) -> "BeamResult":
         """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
         synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
         `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
@@ -275,7 +283,10 @@ class ASTER_V2(InferenceModule):
         `pattern` (evaluation.pattern.DecodePattern; not together with `lexicon`): the search can only spell strings the
         pattern accepts (glass_beam_search_dfa) - the k most likely of them, complete ones only, at most max_word_len - 1
         characters; `segments` and the checks as for a lexicon, and `.words` carries the tags: the word index for
-        `DecodePattern.from_trie`, 0 for a regex, -1 for an absent hypothesis (score -inf, length 0)."""
+        `DecodePattern.from_trie`, 0 for a regex, -1 for an absent hypothesis (score -inf, length 0).
+        A `WeightedPattern` (evaluation.weighted_pattern) runs glass_beam_search_wdfa: the hypotheses are ranked by the model
+        score + `weight_scale` * the weights of the automaton; `.scores` are these fused scores, `.model_scores` the model's
+        own, and the path rows (and the replayed distributions) are made from the model's, as without weights."""
         if distributions not in (None, "best", "all"):
             raise ValueError(f'beam_decode: distributions must be None, "best" or "all" (got {distributions!r})')
         if lexicon is not None and pattern is not None:
@@ -288,8 +299,13 @@ class ASTER_V2(InferenceModule):
         if pattern is not None:
             seg = self._lexicon_segments(pattern, segments, B, eos, x.device, what="pattern")
         xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x      # empty batch: empty results
-        words = None
-        if pattern is not None:
+        words = model_scores = None
+        from ...evaluation.weighted_pattern import WeightedPattern
+        if isinstance(pattern, WeightedPattern):
+            out = K.beam_search_wdfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
+                                     pattern.tensors, seg, weight_scale=float(weight_scale), path_probs=path_probs)
+            model_scores, words, out = out[2], out[4], out[:2] + out[3:4] + out[5:]
+        elif pattern is not None:
             out = K.beam_search_dfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
                                     pattern.tensors, seg, path_probs=path_probs)
             words, out = out[3], out[:3] + out[4:]
@@ -306,7 +322,7 @@ class ASTER_V2(InferenceModule):
             ln = torch.where(torch.isneginf(sc), torch.zeros_like(ln), ln).contiguous()
             dist = K.forced_decode(x, xproj, self.w, sym, ln, self.num_classes, self.max_word_len, int(eos), probs=True)[3]
             dist = dist[:, 0] if distributions == "best" else dist
-        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist, words)
+        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist, words, model_scores)
 
     def forward(self, features: torch.Tensor, labels=None, roi_image: Optional[torch.Tensor] = None,
                 num_images: int = 1, rnn=None, status=None) -> torch.Tensor:

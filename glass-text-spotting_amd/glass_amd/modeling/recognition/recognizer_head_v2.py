@@ -57,6 +57,14 @@ class RecognizerRCNNHeadV3(InferenceModule):
             from ...evaluation.pattern import DecodePattern
             self.set_pattern(DecodePattern(regex, self.text_encoder, self.decoder.max_word_len, self.beam_eos,
                                            device=cfg.MODEL.DEVICE))
+        # MI355X build only: with DECODE_PATTERN, a non-zero bonus per character (a natural log) makes the pattern a
+        # WeightedPattern: the search ranks by the model score + the bonus times the characters (glass_beam_search_wdfa)
+        bonus = float(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "DECODE_LENGTH_BONUS", 0.0) or 0.0)
+        if bonus != 0.0:
+            if not regex:
+                raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.DECODE_LENGTH_BONUS needs MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN "
+                                 "(the bonus is a weight on the pattern's transitions)")
+            self.set_pattern(self.pattern.weighted(length_bonus=bonus))
 
     def import_weights(self, sd, device, prefix: str) -> None:
         self.backbone.import_weights(sd, device, prefix + "backbone.")
@@ -94,14 +102,19 @@ class RecognizerRCNNHeadV3(InferenceModule):
         self.lexicon, self.image_segments = trie, image_segments
 
     pattern = None            # set_pattern: the DecodePattern the search is constrained to (image_segments: its segments)
+    weight_scale = 1.0        # set_pattern: the factor of a WeightedPattern's weights in the score the search ranks by
 
-    def set_pattern(self, pattern, image_segments=None) -> None:
+    def set_pattern(self, pattern, image_segments=None, weight_scale: float = 1.0) -> None:
         """Constrain the decoding to a pattern (evaluation.pattern.DecodePattern; None switches it off): every RoI decodes to
         the most likely string its image's segment accepts (glass_beam_search_dfa), handed on as path rows exactly as the
         unconstrained search's - a RoI with no hypothesis gets all-zero rows.  `image_segments` as in set_lexicon.
+        With a `WeightedPattern` (glass_beam_search_wdfa) the best string is the one with the highest model score +
+        `weight_scale` * weights; its path rows are still the model's conditional probabilities, so the word score read from
+        them stays a probability.
         ValueError unless BEAM_WIDTH >= 1, if the pattern does not fit the decoder, and while a lexicon is set."""
         if pattern is None:
             self.pattern = self.image_segments = None
+            self.weight_scale = 1.0
             return
         if self.lexicon is not None:
             raise ValueError("set_pattern: a lexicon is set (set_lexicon(None) first)")
@@ -116,7 +129,7 @@ class RecognizerRCNNHeadV3(InferenceModule):
             if (not torch.is_tensor(image_segments) or image_segments.device.type == "cpu" or image_segments.dtype != torch.int32
                     or image_segments.dim() != 1):
                 raise ValueError("set_pattern: image_segments must be an int32 [num_images] tensor on the device")
-        self.pattern, self.image_segments = pattern, image_segments
+        self.pattern, self.image_segments, self.weight_scale = pattern, image_segments, float(weight_scale)
 
     def _roi_segments(self, roi_image: torch.Tensor, num_images: int) -> torch.Tensor:
         if self.image_segments is None:
@@ -147,7 +160,8 @@ class RecognizerRCNNHeadV3(InferenceModule):
             if self.beam_width > 0:         # the search has no in-kernel hand-off: only the encoder is guarded
                 lex = {} if self.lexicon is None else {"lexicon": self.lexicon, "segments": self._roi_segments(roi_image, num_images)}
                 if self.pattern is not None:
-                    lex = {"pattern": self.pattern, "segments": self._roi_segments(roi_image, num_images)}
+                    lex = {"pattern": self.pattern, "segments": self._roi_segments(roi_image, num_images),
+                           "weight_scale": self.weight_scale}
                 if self.beam_distributions:
                     r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best", **lex)
                     return r.path_probs, r.distributions

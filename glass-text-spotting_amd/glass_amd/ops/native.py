@@ -1500,6 +1500,57 @@ def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_wi
     return (symbols, scores, lengths, tags, path) if path_probs else (symbols, scores, lengths, tags)
 
 
+def beam_search_wdfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
+                     eos: int, wdfa: dict, item_pattern: torch.Tensor, weight_scale: float = 1.0, path_probs: bool = False):
+    """the beam search constrained by a WEIGHTED automaton (glass_beam_search_wdfa): as `beam_search_dfa`, with `wdfa` - the
+    device tensors trans int32 [N,F,2] (per entry: next as in `beam_search_dfa`, then the bits of the float32 weight), final_w
+    float32 [N], start_w float32 [S], accept int32 [N], start int32 [S], fold int32 [C] and the int F
+    (evaluation.pattern.WeightedPattern.tensors) - and `weight_scale`, the factor of the weight sum in the score the beams are
+    ranked by -> (symbols int32 [B,k,max_len], fused scores [B,k], model scores [B,k], lengths int32 [B,k], tags int32 [B,k][,
+    path rows [B,max_len,C], made from the model scores]).  No host synchronisation; limits are checked by the library."""
+    B, T, D, dev = _search_inputs("beam_search_wdfa", x, xproj)
+    k, C, L = int(beam_width), int(num_classes), int(max_len)
+    F = int(wdfa["F"])
+    arrays = {n: wdfa.get(n) for n in ("trans", "final_w", "start_w", "accept", "start", "fold")}
+    N = S = 0
+    for n, t in arrays.items():
+        if t is None:
+            continue
+        _f32c(t, n) if n in ("final_w", "start_w") else _i32(t, n)
+        if t.device != dev:
+            raise GlassLibraryError(f"beam_search_wdfa: {n} on {t.device}, x on {dev}")
+    if arrays["trans"] is not None:
+        tr = arrays["trans"]
+        N = int(tr.shape[0])
+        if tr.dim() != 3 or tr.shape[2] != 2 or (1 <= F <= 256 and tr.shape[1] != F):     # (an F outside 1..256 is the library's to refuse)
+            raise GlassLibraryError(f"beam_search_wdfa: trans {tuple(tr.shape)} is not [N, F={F}, 2]")
+        for n in ("accept", "final_w"):
+            if arrays[n] is not None and tuple(arrays[n].shape) != (N,):
+                raise GlassLibraryError(f"beam_search_wdfa: {n} {tuple(arrays[n].shape)} is not [N={N}]")
+    if arrays["start"] is not None:
+        S = int(arrays["start"].numel())
+        if arrays["start_w"] is not None and tuple(arrays["start_w"].shape) != (S,):
+            raise GlassLibraryError(f"beam_search_wdfa: start_w {tuple(arrays['start_w'].shape)} is not [S={S}]")
+    if arrays["fold"] is not None and tuple(arrays["fold"].shape) != (C,):
+        raise GlassLibraryError(f"beam_search_wdfa: fold {tuple(arrays['fold'].shape)} is not [C={C}]")
+    _i32(item_pattern, "item_pattern")
+    if tuple(item_pattern.shape) != (B,) or item_pattern.device != dev:
+        raise GlassLibraryError(f"beam_search_wdfa: item_pattern {tuple(item_pattern.shape)} on {item_pattern.device} is not [B={B}] on {dev}")
+    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
+    model_scores = torch.empty_like(scores)
+    tags = torch.empty_like(lengths)
+    w = _decoder_weights(weights)
+    nbytes = int(lib().glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, L))
+    ws = _workspace(nbytes, dev)
+    check(lib().glass_beam_search_wdfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _opt(arrays["trans"]),
+                                       _opt(arrays["final_w"]), _opt(arrays["start_w"]), _opt(arrays["accept"]),
+                                       _opt(arrays["start"]), _opt(arrays["fold"]), N, S, F, _opt(item_pattern),
+                                       float(weight_scale), _dev(symbols), _dev(scores), _dev(model_scores), _dev(lengths),
+                                       _dev(tags), _opt(path), _dev(ws), nbytes, stream_handle()), "glass_beam_search_wdfa")
+    out = (symbols, scores, model_scores, lengths, tags)
+    return out + (path,) if path_probs else out
+
+
 def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: torch.Tensor, lengths: Optional[torch.Tensor],
                   num_classes: int, max_len: int, eos: int, probs: bool = False, logits: bool = False):
     """the decoder with the emitted symbols given (glass_forced_decode; reference AttentionRecognitionHead.forward): x, xproj
