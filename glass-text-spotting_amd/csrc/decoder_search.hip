@@ -5,6 +5,7 @@
 #include "decoder_common.h"
 #include "glass_hip_ext.h"
 #include "glass_hip_feature_dfa.h"
+#include "glass_hip_feature_merged.h"
 #include "glass_hip_feature_wdfa.h"
 
 // ================================================================== beam search (AttentionRecognitionHead.beam_search)
@@ -505,11 +506,23 @@ struct WdfaParams {
   }
 };
 
+// A constraint with the fold groups of a merged search (glass_hip_feature_merged.h): the classes of fold symbol f are
+// group_cls[group_start[f] .. group_start[f + 1]), ascending.  What con_step_kernel<KB, Merged<CP>, true> reads next to CP's own.
+template <class CP>
+struct Merged : CP {
+  const int* group_start;           // [F + 1]
+  const int* group_cls;             // [n_group_cls]
+  int n_group_cls;
+};
+
 // beam_step_kernel with the mask of a constraint CP (LexParams: the trie, DfaParams: the automaton, WdfaParams: the weighted
 // automaton, whose extra work is all under `if constexpr (CP::weighted)`: the other two kernels are what they were).  Thread u owns class u:
 // its k mask words or table entries (one per beam) are loaded once per step into the bit set `allow`; the k node ids live in
 // LDS.  After the selection, thread j moves slot j to its child node / target state.
-template <int KB, class CP>
+// MERGE (CP = Merged<...>): between the running scores and the top-k, the candidates of one beam whose classes share a fold
+// symbol become ONE candidate - the group's arg-max class (ties: the lowest) carries the log of the group's summed mass, the
+// other members lose their `allow` bit; the merged scores pass through sproj (idle at that point), so cand needs no second copy.  All of it is under `if constexpr (MERGE)`: the unmerged kernels are the code they were.
+template <int KB, class CP, bool MERGE = false>
 __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams bp, CP lp, const float* __restrict__ hraw,
                                                        int step) {
   __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
@@ -593,9 +606,67 @@ __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams b
         }
       }
     }
+    // MERGE: thread u's group [g0, g1) of group_cls, loaded here so that the loads overlap the log-softmax; left empty for the
+    // stop, a class without a fold symbol, a one-class group (its candidate stays bit for bit) and a range outside the array.
+    // c0, c1: the members of a group of two (a letter's two cases), kept in registers; a larger group is re-read row by row.
+    // Every entry is range-checked before it indexes cand.
+    [[maybe_unused]] int g0 = 0, g1 = 0, c0 = -1, c1 = -1;
+    if constexpr (MERGE) {
+      if (u < C && u != bp.eos) {
+        const int f = lp.fold[u];
+        if (f >= 0 && f < lp.F) {
+          const int a = lp.group_start[f], e = lp.group_start[f + 1];
+          if (a >= 0 && e <= lp.n_group_cls && e - a >= 2) {
+            g0 = a; g1 = e;
+            if (e - a == 2) { c0 = lp.group_cls[a]; c1 = lp.group_cls[a + 1]; }
+          }
+        }
+      }
+    }
     __syncthreads();
     rows_score<KB>(k, C, lane, wave, run, cand);
     __syncthreads();
+    if constexpr (MERGE) {
+      // every member reads its rows (is it the arg-max?  then the sum, in ascending class order) and parks the merged score in
+      // sproj, which is idle until rows_attend; ONE barrier; only then the representatives overwrite their cells - cells the
+      // other members have read to decide.  Nothing but the flags `rep` lives across the barrier.
+      const bool pair = g1 - g0 == 2;
+      unsigned rep = 0u;
+#pragma unroll
+      for (int r = 0; r < KB; ++r) {
+        if (r < k && g1 > g0) {
+          float top = -INFINITY;
+          int at = -1;
+          for (int i = g0; i < g1; ++i) {
+            const int c = pair ? (i == g0 ? c0 : c1) : lp.group_cls[i];
+            if (c >= 0 && c < C) {
+              const float v = cand[r][c];
+              if (at < 0 || v > top) { top = v; at = c; }
+            }
+          }
+          if (at == u) {
+            float s = top;                                               // an all -inf group stays -inf
+            if (top > -INFINITY) {
+              float sum = 0.f;
+              for (int i = g0; i < g1; ++i) {
+                const int c = pair ? (i == g0 ? c0 : c1) : lp.group_cls[i];
+                if (c >= 0 && c < C) sum += expf(cand[r][c] - top);      // a member at -inf adds 0
+              }
+              s = top + logf(sum);
+            }
+            sproj[r][u] = s;
+            rep |= 1u << r;
+          } else {
+            allow &= ~(1u << r);
+          }
+        }
+      }
+      __syncthreads();
+#pragma unroll
+      for (int r = 0; r < KB; ++r)
+        if ((rep >> r) & 1u) cand[r][u] = sproj[r][u];
+      // (no barrier: the top-k reads cand[r][u] in thread u only, which wrote it)
+    }
     if constexpr (CP::weighted) {
       // cand stays the model candidates; the top-k ranks them fused with the thread's k weight terms
       rows_topk_by<KB>(k, C, u, lane, wave, allow, [&](int r) { return lp.fuse(cand[r][u], term[r]); }, wbest, wbesti,
@@ -791,20 +862,31 @@ extern "C" int64_t glass_beam_search_dfa_workspace_bytes(int B, int k, int T, in
   return glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len);
 }
 
-extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
-                                     int C, int max_len, int eos, const int* next, const int* accept, const int* start,
-                                     const int* fold, int N, int S, int F, const int* item_pattern, int* out_symbols,
-                                     float* out_scores, int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
-                                     int64_t workspace_bytes, glass_stream_t stream) {
-  if (int rc = search_limits("glass_beam_search_dfa", true, B, k, T, D, C, max_len)) return rc;
+// the fold groups of a merged search, checked as far as the host can without reading device memory
+struct FoldGroups { const int* start; const int* cls; int n; };
+static int merged_limits(const char* fn, const FoldGroups& g, int C) {
+  GLASS_CHECK_ARG(g.start && g.cls, "%s: null group array", fn);
+  GLASS_CHECK_ARG(g.n >= 1 && g.n <= C, "%s: needs 1<=n_group_cls<=C (got n_group_cls=%d C=%d)", fn, g.n, C);
+  return GLASS_OK;
+}
+
+// glass_beam_search_dfa (groups == nullptr) and glass_beam_search_merged_dfa; fn = the entry point's name, for the messages
+static int dfa_search(const char* fn, const FoldGroups* groups, const float* x, const float* xproj, const glass_decoder_weights* w,
+                      int B, int k, int T, int D, int C, int max_len, int eos, const int* next, const int* accept, const int* start,
+                      const int* fold, int N, int S, int F, const int* item_pattern, int* out_symbols, float* out_scores,
+                      int* out_lengths, int* out_tags, float* out_path_probs, void* workspace, int64_t workspace_bytes,
+                      glass_stream_t stream) {
+  if (int rc = search_limits(fn, true, B, k, T, D, C, max_len)) return rc;
   GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256,
-                  "glass_beam_search_dfa: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", N, S, F);
+                  "%s: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", fn, N, S, F);
+  if (groups != nullptr)
+    if (int rc = merged_limits(fn, *groups, C)) return rc;
   if (B == 0) return GLASS_OK;
   GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && out_tags && workspace,
-                  "glass_beam_search_dfa: null pointer");
-  GLASS_CHECK_ARG(next && accept && start && fold && item_pattern, "glass_beam_search_dfa: null automaton array");
+                  "%s: null pointer", fn);
+  GLASS_CHECK_ARG(next && accept && start && fold && item_pattern, "%s: null automaton array", fn);
   GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len),
-                  "glass_beam_search_dfa: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  "%s: workspace too small (%lld < %lld bytes)", fn, (long long)workspace_bytes,
                   (long long)glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len));
   hipStream_t s = (hipStream_t)stream;
   DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
@@ -818,21 +900,54 @@ extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const g
   LexParams fin = {};                                                              // what lex_final_kernel reads: nd, N, node_word
   fin.nd = dp.nd; fin.N = N; fin.node_word = accept;
   hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("glass_beam_search_dfa: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  if (e != hipSuccess) { glass_set_error("%s: memset: %s", fn, hipGetErrorString(e)); return GLASS_EHIP; }
   const dim3 gb(B);
+  Merged<DfaParams> mp = {};
+  static_cast<DfaParams&>(mp) = dp;
+  if (groups != nullptr) { mp.group_start = groups->start; mp.group_cls = groups->cls; mp.n_group_cls = groups->n; }
   auto dfa_step = [&](int step) {
-    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL((con_step_kernel<decltype(kb)::value, DfaParams>), gb, dim3(256), 0, s, p, bp, dp, hraw, step); });
+    with_row_block(k, [&](auto kb) {
+      constexpr int KB = decltype(kb)::value;
+      if (groups != nullptr) hipLaunchKernelGGL((con_step_kernel<KB, Merged<DfaParams>, true>), gb, dim3(256), 0, s, p, bp, mp, hraw, step);
+      else hipLaunchKernelGGL((con_step_kernel<KB, DfaParams>), gb, dim3(256), 0, s, p, bp, dp, hraw, step);
+    });
   };
   dfa_step(-1);                                                                   // attention for step 0
   for (int step = 0; step < max_len; ++step) {
     dec_gru_step(p, hsel, hraw, s);
     dfa_step(step);
   }
-  GLASS_CHECK_LAUNCH("glass_beam_search_dfa");
+  GLASS_CHECK_LAUNCH(fn);
   hipLaunchKernelGGL(lex_final_kernel<false>, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags,
                      out_path_probs, (const float*)nullptr, (float*)nullptr);
-  GLASS_CHECK_LAUNCH("glass_beam_search_dfa(final)");
+  GLASS_CHECK_LAUNCH(fn);
   return GLASS_OK;
+}
+
+extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
+                                     int C, int max_len, int eos, const int* next, const int* accept, const int* start,
+                                     const int* fold, int N, int S, int F, const int* item_pattern, int* out_symbols,
+                                     float* out_scores, int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
+                                     int64_t workspace_bytes, glass_stream_t stream) {
+  return dfa_search("glass_beam_search_dfa", nullptr, x, xproj, w, B, k, T, D, C, max_len, eos, next, accept, start, fold, N, S, F,
+                    item_pattern, out_symbols, out_scores, out_lengths, out_tags, out_path_probs, workspace, workspace_bytes, stream);
+}
+
+// ---- the merged twin (glass_hip_feature_merged.h): the same search with MERGE in its step kernel, the same workspace
+extern "C" int64_t glass_beam_search_merged_dfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  return glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len);
+}
+
+extern "C" int glass_beam_search_merged_dfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
+                                            int D, int C, int max_len, int eos, const int* next, const int* accept, const int* start,
+                                            const int* fold, int N, int S, int F, const int* item_pattern, const int* group_start,
+                                            const int* group_cls, int n_group_cls, int* out_symbols, float* out_scores,
+                                            int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
+                                            int64_t workspace_bytes, glass_stream_t stream) {
+  const FoldGroups groups = {group_start, group_cls, n_group_cls};
+  return dfa_search("glass_beam_search_merged_dfa", &groups, x, xproj, w, B, k, T, D, C, max_len, eos, next, accept, start, fold, N,
+                    S, F, item_pattern, out_symbols, out_scores, out_lengths, out_tags, out_path_probs, workspace, workspace_bytes,
+                    stream);
 }
 
 // ================================================================== weighted-automaton beam search (glass_hip_feature_wdfa.h)
@@ -844,26 +959,29 @@ extern "C" int64_t glass_beam_search_wdfa_workspace_bytes(int B, int k, int T, i
   return glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len) + (int64_t)2 * B * max_len * k * (int64_t)sizeof(float);
 }
 
-extern "C" int glass_beam_search_wdfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
-                                      int C, int max_len, int eos, const glass_wdfa_transition* trans, const float* final_w,
-                                      const float* start_w, const int* accept, const int* start, const int* fold, int N, int S,
-                                      int F, const int* item_pattern, float weight_scale, int* out_symbols, float* out_scores,
-                                      float* out_model_scores, int* out_lengths, int* out_tags, float* out_path_probs,
-                                      void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
+// glass_beam_search_wdfa (groups == nullptr) and glass_beam_search_merged_wdfa
+static int wdfa_search(const char* fn, const FoldGroups* groups, const float* x, const float* xproj, const glass_decoder_weights* w,
+                       int B, int k, int T, int D, int C, int max_len, int eos, const glass_wdfa_transition* trans,
+                       const float* final_w, const float* start_w, const int* accept, const int* start, const int* fold, int N, int S,
+                       int F, const int* item_pattern, float weight_scale, int* out_symbols, float* out_scores,
+                       float* out_model_scores, int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
+                       int64_t workspace_bytes, glass_stream_t stream) {
   static_assert(sizeof(glass_wdfa_transition) == 8 && offsetof(glass_wdfa_transition, w) == 4, "one 64-bit load per table entry");
-  if (int rc = search_limits("glass_beam_search_wdfa", true, B, k, T, D, C, max_len)) return rc;
+  if (int rc = search_limits(fn, true, B, k, T, D, C, max_len)) return rc;
   GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256,
-                  "glass_beam_search_wdfa: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", N, S, F);
+                  "%s: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", fn, N, S, F);
   GLASS_CHECK_ARG(weight_scale == weight_scale && weight_scale - weight_scale == 0.f,
-                  "glass_beam_search_wdfa: weight_scale must be finite (got %g)", (double)weight_scale);
+                  "%s: weight_scale must be finite (got %g)", fn, (double)weight_scale);
+  if (groups != nullptr)
+    if (int rc = merged_limits(fn, *groups, C)) return rc;
   if (B == 0) return GLASS_OK;
   GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_model_scores && out_lengths && out_tags && workspace,
-                  "glass_beam_search_wdfa: null pointer");
+                  "%s: null pointer", fn);
   GLASS_CHECK_ARG(trans && final_w && start_w && accept && start && fold && item_pattern,
-                  "glass_beam_search_wdfa: null automaton array");
-  GLASS_CHECK_ARG((reinterpret_cast<uintptr_t>(trans) & 7u) == 0, "glass_beam_search_wdfa: trans is not 8-byte aligned");
+                  "%s: null automaton array", fn);
+  GLASS_CHECK_ARG((reinterpret_cast<uintptr_t>(trans) & 7u) == 0, "%s: trans is not 8-byte aligned", fn);
   GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len),
-                  "glass_beam_search_wdfa: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
+                  "%s: workspace too small (%lld < %lld bytes)", fn, (long long)workspace_bytes,
                   (long long)glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len));
   hipStream_t s = (hipStream_t)stream;
   DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
@@ -882,19 +1000,55 @@ extern "C" int glass_beam_search_wdfa(const float* x, const float* xproj, const 
   LexParams fin = {};                                                              // what lex_final_kernel reads: nd, N, node_word
   fin.nd = wp.nd; fin.N = N; fin.node_word = accept;
   hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("glass_beam_search_wdfa: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  if (e != hipSuccess) { glass_set_error("%s: memset: %s", fn, hipGetErrorString(e)); return GLASS_EHIP; }
   const dim3 gb(B);
+  Merged<WdfaParams> mp = {};
+  static_cast<WdfaParams&>(mp) = wp;
+  if (groups != nullptr) { mp.group_start = groups->start; mp.group_cls = groups->cls; mp.n_group_cls = groups->n; }
   auto wdfa_step = [&](int step) {
-    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL((con_step_kernel<decltype(kb)::value, WdfaParams>), gb, dim3(256), 0, s, p, bp, wp, hraw, step); });
+    with_row_block(k, [&](auto kb) {
+      constexpr int KB = decltype(kb)::value;
+      if (groups != nullptr) hipLaunchKernelGGL((con_step_kernel<KB, Merged<WdfaParams>, true>), gb, dim3(256), 0, s, p, bp, mp, hraw, step);
+      else hipLaunchKernelGGL((con_step_kernel<KB, WdfaParams>), gb, dim3(256), 0, s, p, bp, wp, hraw, step);
+    });
   };
   wdfa_step(-1);                                                                  // attention for step 0
   for (int step = 0; step < max_len; ++step) {
     dec_gru_step(p, hsel, hraw, s);
     wdfa_step(step);
   }
-  GLASS_CHECK_LAUNCH("glass_beam_search_wdfa");
+  GLASS_CHECK_LAUNCH(fn);
   hipLaunchKernelGGL(lex_final_kernel<true>, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags,
                      out_path_probs, (const float*)wp.fu, out_model_scores);
-  GLASS_CHECK_LAUNCH("glass_beam_search_wdfa(final)");
+  GLASS_CHECK_LAUNCH(fn);
   return GLASS_OK;
+}
+
+extern "C" int glass_beam_search_wdfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
+                                      int C, int max_len, int eos, const glass_wdfa_transition* trans, const float* final_w,
+                                      const float* start_w, const int* accept, const int* start, const int* fold, int N, int S,
+                                      int F, const int* item_pattern, float weight_scale, int* out_symbols, float* out_scores,
+                                      float* out_model_scores, int* out_lengths, int* out_tags, float* out_path_probs,
+                                      void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
+  return wdfa_search("glass_beam_search_wdfa", nullptr, x, xproj, w, B, k, T, D, C, max_len, eos, trans, final_w, start_w, accept,
+                     start, fold, N, S, F, item_pattern, weight_scale, out_symbols, out_scores, out_model_scores, out_lengths,
+                     out_tags, out_path_probs, workspace, workspace_bytes, stream);
+}
+
+extern "C" int64_t glass_beam_search_merged_wdfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  return glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len);
+}
+
+extern "C" int glass_beam_search_merged_wdfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
+                                             int D, int C, int max_len, int eos, const glass_wdfa_transition* trans,
+                                             const float* final_w, const float* start_w, const int* accept, const int* start,
+                                             const int* fold, int N, int S, int F, const int* item_pattern, float weight_scale,
+                                             const int* group_start, const int* group_cls, int n_group_cls, int* out_symbols,
+                                             float* out_scores, float* out_model_scores, int* out_lengths, int* out_tags,
+                                             float* out_path_probs, void* workspace, int64_t workspace_bytes,
+                                             glass_stream_t stream) {
+  const FoldGroups groups = {group_start, group_cls, n_group_cls};
+  return wdfa_search("glass_beam_search_merged_wdfa", &groups, x, xproj, w, B, k, T, D, C, max_len, eos, trans, final_w, start_w,
+                     accept, start, fold, N, S, F, item_pattern, weight_scale, out_symbols, out_scores, out_model_scores,
+                     out_lengths, out_tags, out_path_probs, workspace, workspace_bytes, stream);
 }

@@ -156,6 +156,11 @@ def add_e2e_config(cfg: CN) -> None:
     # natural log, on the pattern's transitions: the search ranks by the model score + the bonus times the characters
     # (DecodePattern.weighted(length_bonus=...), glass_beam_search_wdfa); the word score stays the model's probability
     blk["DECODE_LENGTH_BONUS"] = 0.0
+    # MI355X build only: False = off, nothing changes; True (with DECODE_PATTERN; ValueError otherwise) = the head builds its
+    # pattern with case_insensitive=True and the search merges the two cases of a letter into one candidate per beam
+    # (RecognizerRCNNHeadV3.set_pattern(merge_case=True), include/glass_hip_feature_merged.h): k distinct folded strings, and
+    # the word score is the probability of the word, not of one casing
+    blk["DECODE_MERGE_CASE"] = False
     cfg.MODEL.merge_from_other_cfg({"ROI_RECOGNIZER_HEAD": blk})
 
 

@@ -7,7 +7,7 @@ from typing import Callable, Dict, List, Optional, Sequence
 
 def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[[Dict], Dict], writer=None,
                          batch_size: int = 8, lexicon=None, lexicon_key: Optional[Callable[[Dict], object]] = None, pattern=None,
-                         pattern_key: Optional[Callable[[Dict], object]] = None) -> List[Dict]:
+                         pattern_key: Optional[Callable[[Dict], object]] = None, merge_case: bool = False) -> List[Dict]:
     """Run `model` over `dataset_dicts` and return its per-image outputs in input order.
 
     The reference evaluates one image per call.  Here up to `batch_size` images share a call, grouped by their own padded
@@ -25,8 +25,14 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
     `pattern` (evaluation.pattern.DecodePattern) / `pattern_key`: the same for pattern-constrained decoding
     (`RecognizerRCNNHeadV3.set_pattern`); a pattern the head had before (MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN) is put back
     afterwards.  Not together with `lexicon`.  A `WeightedPattern` (evaluation.weighted_pattern) is taken as it is, with
-    weight_scale 1; the head's own scale is put back with its pattern."""
+    weight_scale 1; the head's own scale is put back with its pattern.
+
+    `merge_case` (with `lexicon` or `pattern`; ValueError otherwise): the fold-merged search
+    (`set_pattern(..., merge_case=True)` / `set_lexicon(..., merge_case=True)`, which goes through `DecodePattern.from_trie`) -
+    with a case-insensitive table a word's casings are one hypothesis and the word score is the probability of the word."""
     assert batch_size >= 1
+    if merge_case and lexicon is None and pattern is None:
+        raise ValueError("merge_case without a lexicon or a pattern")
     if lexicon is None and lexicon_key is not None:
         raise ValueError("lexicon_key without a lexicon")
     if pattern is None and pattern_key is not None:
@@ -38,15 +44,15 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
         import torch
         from ..ops import native
         head = model.roi_heads.recognizer_head
-        before = (head.lexicon, head.pattern, head.image_segments, head.weight_scale)
+        before = (head.lexicon, head.pattern, head.image_segments, head.weight_scale, head.merge_case)
         head.lexicon = head.pattern = head.image_segments = None
         try:
             if lexicon is not None:
-                head.set_lexicon(lexicon)
+                head.set_lexicon(lexicon, merge_case=bool(merge_case))
             else:
-                head.set_pattern(pattern)
+                head.set_pattern(pattern, merge_case=bool(merge_case))
         except Exception:
-            head.lexicon, head.pattern, head.image_segments, head.weight_scale = before
+            head.lexicon, head.pattern, head.image_segments, head.weight_scale, head.merge_case = before
             raise
     table, table_key = (lexicon, lexicon_key) if lexicon is not None else (pattern, pattern_key)
     d = model.backbone.size_divisibility
@@ -78,5 +84,5 @@ def inference_on_dataset(model, dataset_dicts: Sequence[Dict], mapper: Callable[
             run(group)
     finally:
         if head is not None:
-            head.lexicon, head.pattern, head.image_segments, head.weight_scale = before
+            head.lexicon, head.pattern, head.image_segments, head.weight_scale, head.merge_case = before
     return outputs

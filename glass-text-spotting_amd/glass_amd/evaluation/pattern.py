@@ -412,7 +412,8 @@ class DecodePattern:
         one load per (beam, class) decides a candidate, with no dependent second load;
       `dist` int32 [N]: the fewest symbols to an accepting state (not uploaded; NO_PATH for the one state of an empty automaton);
       `accept` int32 [N]: -1, or a tag >= 0 (0 for a regex, the word index for `from_trie`);
-      `start` int32 [S]: -1 for a segment whose language is empty at this max_len;  `fold` int32 [C].
+      `start` int32 [S]: -1 for a segment whose language is empty at this max_len;  `fold` int32 [C];
+      `group_start` int32 [F + 1], `group_cls` int32: `fold_groups()`, read only by a merged search (merge_case=True).
     Limits (ValueError): N <= 2^24 - 1, `next` at most `table_cap_bytes`, at most `nfa_cap` Thompson states per regex."""
 
     word_state = None         # from_trie only: int32 [words], the state every word of the trie ends at (-1: left out)
@@ -508,7 +509,25 @@ class DecodePattern:
         self.tensors = {"next": torch.from_numpy(self.next).to(self.device), "accept": torch.from_numpy(self.accept).to(self.device),
                         "start": torch.from_numpy(self.start).to(self.device), "fold": torch.from_numpy(self.fold).to(self.device),
                         "F": F}
+        self._upload_groups()
         self.build_seconds = time.perf_counter() - t0
+
+    # ---- the fold groups of a merged search (include/glass_hip_feature_merged.h)
+    def fold_groups(self) -> Tuple[np.ndarray, np.ndarray]:
+        """(group_start int32 [F + 1], group_cls int32 [classes with a fold symbol]) from `self.fold`: the classes of fold
+        symbol f are group_cls[group_start[f]:group_start[f + 1]], ascending - with case_insensitive=True a letter's two cases,
+        otherwise one class each.  The stop and the specials (fold -1) are in no group.  Deterministic: a stable sort."""
+        fold = np.asarray(self.fold, dtype=np.int64)
+        cls = np.nonzero((fold >= 0) & (fold < self.num_fold))[0]
+        cls = cls[np.argsort(fold[cls], kind="stable")]
+        start = np.zeros(self.num_fold + 1, dtype=np.int64)
+        np.cumsum(np.bincount(fold[cls], minlength=self.num_fold), out=start[1:])
+        return start.astype(np.int32), cls.astype(np.int32)
+
+    def _upload_groups(self) -> None:
+        self.group_start, self.group_cls = self.fold_groups()
+        self.tensors["group_start"] = torch.from_numpy(self.group_start).to(self.device)
+        self.tensors["group_cls"] = torch.from_numpy(self.group_cls).to(self.device)
 
     # ---- the other constructors
     @classmethod

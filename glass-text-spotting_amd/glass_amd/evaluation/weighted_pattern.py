@@ -189,7 +189,8 @@ class WeightedPattern(DecodePattern):
         `start64` float64 [S] (0 for a segment without a start state);
       `trans` int32 [N,F,2]: `next`, then the bits of float32(weight64);  `final_w` / `start_w`: float32 of the other two;
       `base_state` int32 [N]: the state of the pattern it was built from;  `contexts`: with an `lm`, every state's context;
-      `tensors`: trans, final_w, start_w, accept, start, fold on the device, and the int "F".
+      `tensors`: trans, final_w, start_w, accept, start, fold (and the fold groups, group_start / group_cls) on the device,
+        and the int "F".
     Limits (ValueError): N <= 2^24 - 1, `trans` at most `table_cap_bytes`."""
 
     def __init__(self, base: DecodePattern, lm: Optional[CharNgramLM] = None, word_logprior=None, length_bonus: float = 0.0,
@@ -254,6 +255,7 @@ class WeightedPattern(DecodePattern):
         self.tensors = {n: torch.from_numpy(getattr(self, n)).to(self.device) for n in ("trans", "final_w", "start_w", "accept", "start",
                                                                                         "fold")}
         self.tensors["F"] = F
+        self._upload_groups()
         self.build_seconds = time.perf_counter() - t0
 
     # ---- word priors, pushed toward the root

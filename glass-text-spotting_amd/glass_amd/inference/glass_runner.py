@@ -142,7 +142,8 @@ class GlassRunner:
         return out
 
     def run_tiled(self, image: np.ndarray, tile: int = 1024, overlap: int = 256, border: int = 16, scale: float = 1.0,
-                  full_view: bool = True, nms_thresh: Optional[float] = None, batch_size: int = 8) -> Instances:
+                  full_view: bool = True, nms_thresh: Optional[float] = None, batch_size: int = 8,
+                  merge_case: Optional[bool] = None) -> Instances:
         """One large image at (`scale` times) its own resolution: `__call__` shrinks an image whose long side exceeds
         INPUT.MAX_SIZE_TEST, and the small words of a scan or a receipt are gone before the RPN sees them.  Here the image is cut
         into overlapping tiles (tiling.plan_tiles) that run through the model as batches of at most `batch_size`; with
@@ -152,8 +153,22 @@ class GlassRunner:
         L = overlap - 2*border, a word of the full view if its extent is above L, and of the copies of a word that several views
         hold the best-scored one stays (rotated IoU >= `nms_thresh`, default MODEL.ROI_HEADS.NMS_THRESH_TEST, between boxes of
         different views).  The merged set - at most 1024 detections - then takes the ordinary way through the word
-        post-processor, with the boxes in the original image's pixels."""
+        post-processor, with the boxes in the original image's pixels.
+        `merge_case` (None: the recogniser head's own setting): run every view with the head's pattern searched fold-merged
+        (True) or unmerged (False) - `RecognizerRCNNHeadV3.set_pattern(merge_case=...)` for this call only; ValueError if the
+        head has no pattern."""
         heads = self.model.roi_heads
+        if merge_case is not None:
+            head = getattr(heads, "recognizer_head", None)
+            if getattr(head, "pattern", None) is None:
+                raise ValueError("run_tiled: merge_case needs a pattern on the recogniser head (set_pattern, or "
+                                 "set_lexicon(trie, merge_case=True))")
+            before = head.merge_case
+            head.merge_case = bool(merge_case)
+            try:
+                return self.run_tiled(image, tile, overlap, border, scale, full_view, nms_thresh, batch_size)
+            finally:
+                head.merge_case = before
         with_masks = bool(getattr(heads, "mask_inference", False))
         if with_masks and getattr(self.model, "paste_masks", True):
             raise NotImplementedError("run_tiled: MODEL.ROI_MASK_HEAD.MASK_INFERENCE is on and the masks are pasted per tile frame, "

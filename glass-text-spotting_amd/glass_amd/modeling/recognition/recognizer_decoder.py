@@ -263,7 +263,7 @@ class ASTER_V2(InferenceModule):
 
     def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False,
                     distributions: Optional[str] = None, lexicon=None, segments=None, pattern=None,
-                    weight_scale: float = 1.0) -> "BeamResult":
+                    weight_scale: float = 1.0, merge_case: bool = False) -> "BeamResult":
         """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
         synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
         `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
@@ -286,7 +286,19 @@ class ASTER_V2(InferenceModule):
         `DecodePattern.from_trie`, 0 for a regex, -1 for an absent hypothesis (score -inf, length 0).
         A `WeightedPattern` (evaluation.weighted_pattern) runs glass_beam_search_wdfa: the hypotheses are ranked by the model
         score + `weight_scale` * the weights of the automaton; `.scores` are these fused scores, `.model_scores` the model's
-        own, and the path rows (and the replayed distributions) are made from the model's, as without weights."""
+        own, and the path rows (and the replayed distributions) are made from the model's, as without weights.
+        `merge_case` (with `pattern` only; include/glass_hip_feature_merged.h has the contract): the classes of one fold symbol
+        - with a case-insensitive pattern a letter's two cases - are ONE candidate per beam, scored with the log of their
+        summed probability and emitted as the likelier of them, so the k hypotheses are k distinct folded strings and a score
+        is the probability of the word, not of one casing.  The hidden state follows the emitted class only.  With a
+        case-sensitive pattern every group is one class and the result equals the unmerged search bit for bit.  The replayed
+        `distributions` are those of the emitted symbols.  ValueError without `pattern`; with `lexicon=` it names
+        `DecodePattern.from_trie`, the route for a lexicon."""
+        if merge_case and lexicon is not None:
+            raise ValueError("beam_decode: merge_case with lexicon= (pass pattern=DecodePattern.from_trie(lexicon): the merged "
+                             "search runs on the pattern tables)")
+        if merge_case and pattern is None:
+            raise ValueError("beam_decode: merge_case needs pattern= (the groups are the pattern's fold symbols)")
         if distributions not in (None, "best", "all"):
             raise ValueError(f'beam_decode: distributions must be None, "best" or "all" (got {distributions!r})')
         if lexicon is not None and pattern is not None:
@@ -303,11 +315,12 @@ class ASTER_V2(InferenceModule):
         from ...evaluation.weighted_pattern import WeightedPattern
         if isinstance(pattern, WeightedPattern):
             out = K.beam_search_wdfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
-                                     pattern.tensors, seg, weight_scale=float(weight_scale), path_probs=path_probs)
+                                     pattern.tensors, seg, weight_scale=float(weight_scale), path_probs=path_probs,
+                                     merge=bool(merge_case))
             model_scores, words, out = out[2], out[4], out[:2] + out[3:4] + out[5:]
         elif pattern is not None:
             out = K.beam_search_dfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
-                                    pattern.tensors, seg, path_probs=path_probs)
+                                    pattern.tensors, seg, path_probs=path_probs, merge=bool(merge_case))
             words, out = out[3], out[:3] + out[4:]
         elif lexicon is not None:
             out = K.beam_search_lexicon(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),

@@ -48,15 +48,22 @@ class RecognizerRCNNHeadV3(InferenceModule):
             raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.BEAM_DISTRIBUTIONS needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 "
                              f"(got BEAM_WIDTH {self.beam_width}): the greedy decoder's pred_text_prob already holds full rows")
         # MI355X build only: a non-empty regex constrains the search to it from construction on (set_pattern with a
-        # one-segment, case-sensitive evaluation.pattern.DecodePattern)
+        # one-segment evaluation.pattern.DecodePattern, case-sensitive unless DECODE_MERGE_CASE)
         regex = str(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "DECODE_PATTERN", "") or "")
+        # MI355X build only: with DECODE_PATTERN, the pattern is built case-insensitive and the search merges the two cases of
+        # a letter into one candidate (set_pattern(merge_case=True), include/glass_hip_feature_merged.h): the word score is the
+        # probability of the word, not of one casing
+        merge = bool(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "DECODE_MERGE_CASE", False))
+        if merge and not regex:
+            raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.DECODE_MERGE_CASE needs MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN "
+                             "(the merged search runs on a pattern)")
         if regex:
             if self.beam_width < 1:
                 raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN needs MODEL.ROI_RECOGNIZER_HEAD.BEAM_WIDTH >= 1 "
                                  f"(got BEAM_WIDTH {self.beam_width}): the greedy decoder does not search")
             from ...evaluation.pattern import DecodePattern
             self.set_pattern(DecodePattern(regex, self.text_encoder, self.decoder.max_word_len, self.beam_eos,
-                                           device=cfg.MODEL.DEVICE))
+                                           case_insensitive=merge, device=cfg.MODEL.DEVICE), merge_case=merge)
         # MI355X build only: with DECODE_PATTERN, a non-zero bonus per character (a natural log) makes the pattern a
         # WeightedPattern: the search ranks by the model score + the bonus times the characters (glass_beam_search_wdfa)
         bonus = float(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "DECODE_LENGTH_BONUS", 0.0) or 0.0)
@@ -64,7 +71,7 @@ class RecognizerRCNNHeadV3(InferenceModule):
             if not regex:
                 raise ValueError("MODEL.ROI_RECOGNIZER_HEAD.DECODE_LENGTH_BONUS needs MODEL.ROI_RECOGNIZER_HEAD.DECODE_PATTERN "
                                  "(the bonus is a weight on the pattern's transitions)")
-            self.set_pattern(self.pattern.weighted(length_bonus=bonus))
+            self.set_pattern(self.pattern.weighted(length_bonus=bonus), merge_case=merge)
 
     def import_weights(self, sd, device, prefix: str) -> None:
         self.backbone.import_weights(sd, device, prefix + "backbone.")
@@ -74,12 +81,21 @@ class RecognizerRCNNHeadV3(InferenceModule):
     lexicon = None            # set_lexicon: the LexiconTrie the search is constrained to
     image_segments = None     # set_lexicon: int32 [num_images] on the device, the lexicon segment of every image of a call
 
-    def set_lexicon(self, trie, image_segments=None) -> None:
+    def set_lexicon(self, trie, image_segments=None, merge_case: bool = False) -> None:
         """Constrain the decoding to a lexicon (evaluation.lexicon.LexiconTrie; None switches it off): every RoI decodes to
         the most likely word of its image's segment (glass_beam_search_lexicon), handed on as path rows exactly as the
         unconstrained search's - a RoI for which no word completes gets all-zero rows (an empty text with score 0).
         `image_segments`: int32 [num_images] on the device (default: segment 0 for every image); it is gathered by the
-        RoIs' image ids on the device.  ValueError unless BEAM_WIDTH >= 1, and if the trie does not fit the decoder."""
+        RoIs' image ids on the device.  `merge_case`: the fold-merged search (set_pattern has the meaning) - it runs on the
+        pattern tables, so the head goes through `set_pattern(DecodePattern.from_trie(trie), merge_case=True)`: `pattern` is
+        set, `lexicon` stays None.  ValueError unless BEAM_WIDTH >= 1, and if the trie does not fit the decoder."""
+        if trie is not None and merge_case:
+            if self.lexicon is not None:
+                raise ValueError("set_lexicon(merge_case=True): a lexicon is set (set_lexicon(None) first)")
+            from ...evaluation.pattern import DecodePattern
+            self.set_pattern(None)
+            self.set_pattern(DecodePattern.from_trie(trie), image_segments, merge_case=True)
+            return
         if trie is None:
             self.lexicon = None
             if self.pattern is None:            # (a pattern's segments are its own)
@@ -103,18 +119,23 @@ class RecognizerRCNNHeadV3(InferenceModule):
 
     pattern = None            # set_pattern: the DecodePattern the search is constrained to (image_segments: its segments)
     weight_scale = 1.0        # set_pattern: the factor of a WeightedPattern's weights in the score the search ranks by
+    merge_case = False        # set_pattern: the search merges the classes of a fold symbol (a letter's two cases)
 
-    def set_pattern(self, pattern, image_segments=None, weight_scale: float = 1.0) -> None:
+    def set_pattern(self, pattern, image_segments=None, weight_scale: float = 1.0, merge_case: bool = False) -> None:
         """Constrain the decoding to a pattern (evaluation.pattern.DecodePattern; None switches it off): every RoI decodes to
         the most likely string its image's segment accepts (glass_beam_search_dfa), handed on as path rows exactly as the
         unconstrained search's - a RoI with no hypothesis gets all-zero rows.  `image_segments` as in set_lexicon.
         With a `WeightedPattern` (glass_beam_search_wdfa) the best string is the one with the highest model score +
         `weight_scale` * weights; its path rows are still the model's conditional probabilities, so the word score read from
         them stays a probability.
+        `merge_case` (ASTER_V2.beam_decode(merge_case=True), include/glass_hip_feature_merged.h): the classes of a fold symbol
+        are one candidate per beam - with a case-insensitive pattern the path rows hold, at the likelier casing of every
+        position, the summed conditional probability of both, and the word score is the probability of the word.
         ValueError unless BEAM_WIDTH >= 1, if the pattern does not fit the decoder, and while a lexicon is set."""
         if pattern is None:
             self.pattern = self.image_segments = None
             self.weight_scale = 1.0
+            self.merge_case = False
             return
         if self.lexicon is not None:
             raise ValueError("set_pattern: a lexicon is set (set_lexicon(None) first)")
@@ -130,6 +151,7 @@ class RecognizerRCNNHeadV3(InferenceModule):
                     or image_segments.dim() != 1):
                 raise ValueError("set_pattern: image_segments must be an int32 [num_images] tensor on the device")
         self.pattern, self.image_segments, self.weight_scale = pattern, image_segments, float(weight_scale)
+        self.merge_case = bool(merge_case)
 
     def _roi_segments(self, roi_image: torch.Tensor, num_images: int) -> torch.Tensor:
         if self.image_segments is None:
@@ -162,6 +184,8 @@ class RecognizerRCNNHeadV3(InferenceModule):
                 if self.pattern is not None:
                     lex = {"pattern": self.pattern, "segments": self._roi_segments(roi_image, num_images),
                            "weight_scale": self.weight_scale}
+                    if self.merge_case:
+                        lex["merge_case"] = True
                 if self.beam_distributions:
                     r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best", **lex)
                     return r.path_probs, r.distributions

@@ -1455,18 +1455,83 @@ def beam_search_lexicon(x: torch.Tensor, xproj: torch.Tensor, weights: dict, bea
     return (symbols, scores, lengths, words, path) if path_probs else (symbols, scores, lengths, words)
 
 
+def check_fold_groups(fold, group_start, group_cls, num_classes: int, num_fold: int, eos: int) -> None:
+    """ValueError unless (group_start [F + 1], group_cls) are fold groups of `fold` [C] as include/glass_hip_feature_merged.h
+    wants them: group_start rises from 0 to len(group_cls) <= C, every entry of group_cls a class in [0, C) other than `eos`,
+    ascending within its group, in at most one group, and with fold equal to its group's symbol.  Host arrays (numpy)."""
+    C, F = int(num_classes), int(num_fold)
+    fold, gs, gc = (np.asarray(a) for a in (fold, group_start, group_cls))
+    for name, a in (("fold", fold), ("group_start", gs), ("group_cls", gc)):
+        if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"fold groups: {name} must be a 1-d integer array (got {a.dtype} {a.shape})")
+    if fold.shape[0] != C:
+        raise ValueError(f"fold groups: fold has {fold.shape[0]} entries, the decoder {C} classes")
+    if gs.shape[0] != F + 1:
+        raise ValueError(f"fold groups: group_start has {gs.shape[0]} entries (needs F + 1 = {F + 1})")
+    n = gc.shape[0]
+    if not 1 <= n <= C:
+        raise ValueError(f"fold groups: group_cls has {n} entries (needs 1..C = {C})")
+    if gs[0] != 0 or gs[-1] != n or (np.diff(gs) < 0).any():
+        raise ValueError(f"fold groups: group_start must rise from 0 to len(group_cls) = {n}")
+    if (gc < 0).any() or (gc >= C).any():
+        raise ValueError(f"fold groups: group_cls holds a class outside [0, {C})")
+    if (gc == int(eos)).any():
+        raise ValueError(f"fold groups: the stop class {int(eos)} is in a group")
+    if len(np.unique(gc)) != n:
+        raise ValueError("fold groups: a class is in more than one group")
+    sym = np.repeat(np.arange(F), np.diff(gs))
+    if (fold[gc] != sym).any():
+        c = int(gc[np.nonzero(fold[gc] != sym)[0][0]])
+        raise ValueError(f"fold groups: class {c} has fold {int(fold[c])}, its group another symbol (fold must be equal within a group)")
+    same = sym[1:] == sym[:-1]
+    if (np.diff(gc)[same] <= 0).any():
+        raise ValueError("fold groups: the classes of a group must be ascending")
+
+
+def _merge_arrays(who: str, tables: dict, arrays: dict, C: int, F: int, eos: int, dev):
+    """the group arrays of a merged search from the tensors dict -> (group_start, group_cls, n) on the device.  Device tensors
+    (a DecodePattern's own) are passed through; HOST arrays (numpy / lists / CPU tensors: hand-made groups, and a hand-made
+    `fold` next to them) are validated with `check_fold_groups` and uploaded - `arrays["fold"]` is replaced by the upload."""
+    gs, gc = tables.get("group_start"), tables.get("group_cls")
+    if gs is None or gc is None:
+        raise GlassLibraryError(f"{who}: merge=True needs group_start and group_cls (DecodePattern.tensors carries them)")
+    host = [n for n, a in (("fold", arrays["fold"]), ("group_start", gs), ("group_cls", gc))
+            if not (torch.is_tensor(a) and a.device.type != "cpu")]
+    if host:
+        fold = arrays["fold"]
+        if fold is None:
+            raise GlassLibraryError(f"{who}: merge=True needs fold")
+        as_np = lambda a: a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+        fold, gs, gc = as_np(fold), as_np(gs), as_np(gc)
+        check_fold_groups(fold, gs, gc, C, F, eos)
+        arrays["fold"] = upload(torch.from_numpy(np.ascontiguousarray(fold, dtype=np.int32)), torch.int32, dev)
+        gs = upload(torch.from_numpy(np.ascontiguousarray(gs, dtype=np.int32)), torch.int32, dev)
+        gc = upload(torch.from_numpy(np.ascontiguousarray(gc, dtype=np.int32)), torch.int32, dev)
+    for n, t in (("group_start", gs), ("group_cls", gc)):
+        _i32(t, n)
+        if t.device != dev:
+            raise GlassLibraryError(f"{who}: {n} on {t.device}, x on {dev}")
+    if tuple(gs.shape) != (F + 1,) or gc.dim() != 1:
+        raise GlassLibraryError(f"{who}: group_start {tuple(gs.shape)} / group_cls {tuple(gc.shape)} are not [F + 1 = {F + 1}] / [n]")
+    return gs, gc, int(gc.numel())
+
+
 def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
-                    eos: int, dfa: dict, item_pattern: torch.Tensor, path_probs: bool = False):
+                    eos: int, dfa: dict, item_pattern: torch.Tensor, path_probs: bool = False, merge: bool = False):
     """the beam search constrained by an automaton (glass_beam_search_dfa): as `beam_search_lexicon`, with `dfa` - the device
     tensors next int32 [N,F] (target | min(dist, 127) << 24, or -1), accept int32 [N], start int32 [S], fold int32 [C] and the
     int F (evaluation.pattern.DecodePattern.tensors) - in the place of the trie, and item_pattern int32 [B] (the segment of
     every item) on x's device -> (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k], tags int32 [B,k][, path rows
     [B,max_len,C]]): the k most likely strings of each item's segment, best first; tags = `accept` of the terminal state.
+    `merge`: the fold-merged search (glass_beam_search_merged_dfa, include/glass_hip_feature_merged.h) - the classes of a fold
+    symbol are one candidate per beam; `dfa` then also holds group_start int32 [F+1] and group_cls int32 [n].  Hand-made
+    groups (and a hand-made `fold`) may be HOST arrays: they are validated (`check_fold_groups`, ValueError) and uploaded.
     No host synchronisation; limits are checked by the library."""
     B, T, D, dev = _search_inputs("beam_search_dfa", x, xproj)
     k, C, L = int(beam_width), int(num_classes), int(max_len)
     F = int(dfa["F"])
     arrays = {n: dfa.get(n) for n in ("next", "accept", "start", "fold")}
+    groups = _merge_arrays("beam_search_dfa", dfa, arrays, C, F, int(eos), dev) if merge else None
     N = S = 0
     for n, t in arrays.items():
         if t is None:
@@ -1491,6 +1556,16 @@ def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_wi
     symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
     tags = torch.empty_like(lengths)
     w = _decoder_weights(weights)
+    if groups is not None:
+        nbytes = int(lib().glass_beam_search_merged_dfa_workspace_bytes(B, k, T, D, C, L))
+        ws = _workspace(nbytes, dev)
+        check(lib().glass_beam_search_merged_dfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos),
+                                                 _opt(arrays["next"]), _opt(arrays["accept"]), _opt(arrays["start"]),
+                                                 _opt(arrays["fold"]), N, S, F, _opt(item_pattern), _dev(groups[0]),
+                                                 _dev(groups[1]), groups[2], _dev(symbols), _dev(scores), _dev(lengths),
+                                                 _dev(tags), _opt(path), _dev(ws), nbytes, stream_handle()),
+              "glass_beam_search_merged_dfa")
+        return (symbols, scores, lengths, tags, path) if path_probs else (symbols, scores, lengths, tags)
     nbytes = int(lib().glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, L))
     ws = _workspace(nbytes, dev)
     check(lib().glass_beam_search_dfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _opt(arrays["next"]),
@@ -1501,17 +1576,20 @@ def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_wi
 
 
 def beam_search_wdfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
-                     eos: int, wdfa: dict, item_pattern: torch.Tensor, weight_scale: float = 1.0, path_probs: bool = False):
+                     eos: int, wdfa: dict, item_pattern: torch.Tensor, weight_scale: float = 1.0, path_probs: bool = False,
+                     merge: bool = False):
     """the beam search constrained by a WEIGHTED automaton (glass_beam_search_wdfa): as `beam_search_dfa`, with `wdfa` - the
     device tensors trans int32 [N,F,2] (per entry: next as in `beam_search_dfa`, then the bits of the float32 weight), final_w
     float32 [N], start_w float32 [S], accept int32 [N], start int32 [S], fold int32 [C] and the int F
     (evaluation.pattern.WeightedPattern.tensors) - and `weight_scale`, the factor of the weight sum in the score the beams are
     ranked by -> (symbols int32 [B,k,max_len], fused scores [B,k], model scores [B,k], lengths int32 [B,k], tags int32 [B,k][,
-    path rows [B,max_len,C], made from the model scores]).  No host synchronisation; limits are checked by the library."""
+    path rows [B,max_len,C], made from the model scores]).  `merge`: as in `beam_search_dfa`
+    (glass_beam_search_merged_wdfa).  No host synchronisation; limits are checked by the library."""
     B, T, D, dev = _search_inputs("beam_search_wdfa", x, xproj)
     k, C, L = int(beam_width), int(num_classes), int(max_len)
     F = int(wdfa["F"])
     arrays = {n: wdfa.get(n) for n in ("trans", "final_w", "start_w", "accept", "start", "fold")}
+    groups = _merge_arrays("beam_search_wdfa", wdfa, arrays, C, F, int(eos), dev) if merge else None
     N = S = 0
     for n, t in arrays.items():
         if t is None:
@@ -1540,6 +1618,18 @@ def beam_search_wdfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_w
     model_scores = torch.empty_like(scores)
     tags = torch.empty_like(lengths)
     w = _decoder_weights(weights)
+    if groups is not None:
+        nbytes = int(lib().glass_beam_search_merged_wdfa_workspace_bytes(B, k, T, D, C, L))
+        ws = _workspace(nbytes, dev)
+        check(lib().glass_beam_search_merged_wdfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos),
+                                                  _opt(arrays["trans"]), _opt(arrays["final_w"]), _opt(arrays["start_w"]),
+                                                  _opt(arrays["accept"]), _opt(arrays["start"]), _opt(arrays["fold"]), N, S, F,
+                                                  _opt(item_pattern), float(weight_scale), _dev(groups[0]), _dev(groups[1]),
+                                                  groups[2], _dev(symbols), _dev(scores), _dev(model_scores), _dev(lengths),
+                                                  _dev(tags), _opt(path), _dev(ws), nbytes, stream_handle()),
+              "glass_beam_search_merged_wdfa")
+        out = (symbols, scores, model_scores, lengths, tags)
+        return out + (path,) if path_probs else out
     nbytes = int(lib().glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, L))
     ws = _workspace(nbytes, dev)
     check(lib().glass_beam_search_wdfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _opt(arrays["trans"]),
