@@ -1,6 +1,8 @@
 // Searches over the attention-GRU decoder of decoder.hip, each behind one ABI call with no host synchronisation: beam search,
-// forced decoding (the symbols given) and the constrained beam searches (a lexicon trie, any DFA, or a weighted DFA).  Per step they run the decoder's GRU launch
-// (dec_gru_step) on all rows and one step kernel, one workgroup per item, composed of the rows_* pieces of decoder_common.h.
+// forced decoding (the symbols given) and the constrained beam searches (a lexicon trie, any DFA, or a weighted DFA; the two
+// automaton searches also fold-merged).  Per step they run the decoder's GRU launch (dec_gru_step) on all rows and one step
+// kernel, one workgroup per item, composed of the rows_* pieces of decoder_common.h.  The six beam searches share one
+// workspace layout (beam_layout) and one host driver (run_beam_search); forced decoding keeps its own loop.
 #include <type_traits>
 #include "decoder_common.h"
 #include "glass_hip_ext.h"
@@ -22,7 +24,7 @@ struct BeamParams {
   int k, L, eos;
 };
 
-// ---- host side, shared by the three searches
+// ---- host side, shared by all the searches
 // f(std::integral_constant<int, KB>) with KB = k rounded up to 1, 2, 4, 8 or 16, the row blocking of the step kernels
 template <class F>
 static void with_row_block(int k, F f) {
@@ -44,24 +46,79 @@ static int search_limits(const char* fn, bool beams, int B, int k, int T, int D,
   return GLASS_OK;
 }
 
-// the workspace of the two beam searches as byte offsets, hsel | hraw | inp | sc | pr | sy (| end: the lexicon search's node
-// table): the *_workspace_bytes functions and beam_carve both read it
-struct BeamLayout { size_t hsel, hraw, inp, sc, pr, sy, end; };
-static BeamLayout beam_layout(int B, int k, int D, int L) {
-  const size_t state = (size_t)B * k * D * sizeof(float), table = (size_t)B * L * k * sizeof(float);   // int tables: as large
+// the workspace of the six beam searches as byte offsets and its size: hsel | hraw | inp (2x) | sc | pr | sy | nd | wa | fu, a
+// state block B*k*D floats, a table B*L*k floats (the int tables are as large).  nd (the constrained searches' node table),
+// wa and fu (the weighted search's weight sums and fused scores) take room only where `has` names them.  Every
+// *_workspace_bytes function and beam_carve read it; a size that is not positive gives the empty layout.
+struct BeamTables { bool nd, wa, fu; };
+constexpr BeamTables BEAM_PLAIN = {false, false, false}, BEAM_NODES = {true, false, false}, BEAM_WEIGHTED = {true, true, true};
+struct BeamLayout { size_t hsel, hraw, inp, sc, pr, sy, nd, wa, fu, total; };
+static BeamLayout beam_layout(int B, int k, int D, int L, BeamTables has) {
+  if (B <= 0 || k <= 0 || D <= 0 || L <= 0) return {};
+  const size_t state = (size_t)B * k * D * sizeof(float), table = (size_t)B * L * k * sizeof(float);
   BeamLayout o;
   o.hsel = 0; o.hraw = o.hsel + state; o.inp = o.hraw + state; o.sc = o.inp + 2 * state; o.pr = o.sc + table; o.sy = o.pr + table;
-  o.end = o.sy + table;
+  o.nd = o.sy + table; o.wa = o.nd + (has.nd ? table : 0); o.fu = o.wa + (has.wa ? table : 0);
+  o.total = o.fu + (has.fu ? table : 0);
   return o;
 }
-// p.h0 = hsel (the GRU's h_prev), p.h1 = hraw (its output), p.inp and the tables of bp point into `workspace`
-static BeamParams beam_carve(void* workspace, const BeamLayout& o, int k, int L, int eos, DecParams& p) {
+// p.h0 = hsel (the GRU's h_prev), p.h1 = hraw (its output), p.inp and the tables of bp point into `workspace`; the tables a
+// search does not have stay null
+struct BeamCarved { BeamParams bp; int* nd; float* wa; float* fu; };
+static BeamCarved beam_carve(void* workspace, const BeamLayout& o, BeamTables has, int k, int L, int eos, DecParams& p) {
   char* ws = static_cast<char*>(workspace);
   p.h0 = reinterpret_cast<float*>(ws + o.hsel); p.h1 = reinterpret_cast<float*>(ws + o.hraw); p.inp = reinterpret_cast<float*>(ws + o.inp);
-  BeamParams bp;
-  bp.sc = reinterpret_cast<float*>(ws + o.sc); bp.pr = reinterpret_cast<int*>(ws + o.pr); bp.sy = reinterpret_cast<int*>(ws + o.sy);
-  bp.hsel = p.h0; bp.k = k; bp.L = L; bp.eos = eos;
-  return bp;
+  BeamCarved c = {};
+  c.bp.sc = reinterpret_cast<float*>(ws + o.sc); c.bp.pr = reinterpret_cast<int*>(ws + o.pr); c.bp.sy = reinterpret_cast<int*>(ws + o.sy);
+  c.bp.hsel = p.h0; c.bp.k = k; c.bp.L = L; c.bp.eos = eos;
+  if (has.nd) c.nd = reinterpret_cast<int*>(ws + o.nd);
+  if (has.wa) c.wa = reinterpret_cast<float*>(ws + o.wa);
+  if (has.fu) c.fu = reinterpret_cast<float*>(ws + o.fu);
+  return c;
+}
+
+// what every beam search's entry point is given; fn = its name, for the messages
+struct SearchArgs {
+  const char* fn;
+  const float *x, *xproj;
+  const glass_decoder_weights* w;
+  int B, k, T, D, C, L, eos;
+  int* out_symbols; float* out_scores; int* out_lengths; float* out_path;
+  void* workspace; int64_t workspace_bytes;
+  hipStream_t stream;
+};
+static int no_check() { return GLASS_OK; }
+
+// The host side of every beam search: the checks in the order the entry points promise (the search's limits, limits() = the
+// family's own, B == 0, null pointers, pointers() = the family's own outputs and arrays, the workspace), the workspace carved
+// and the state zeroed, then attention for step 0, max_len x (GRU launch, step kernel), and the final kernel.
+//   make_step(p, c) -> step(int): the family's step launch (p, c outlive it); final(c): its final launch, named final_fn in
+//   the message of a failed launch
+template <class Limits, class Pointers, class MakeStep, class Final>
+static int run_beam_search(const SearchArgs& a, BeamTables tables, const char* final_fn, Limits limits, Pointers pointers,
+                           MakeStep make_step, Final final) {
+  if (int rc = search_limits(a.fn, true, a.B, a.k, a.T, a.D, a.C, a.L)) return rc;
+  if (int rc = limits()) return rc;
+  if (a.B == 0) return GLASS_OK;
+  GLASS_CHECK_ARG(a.x && a.xproj && a.w && a.out_symbols && a.out_scores && a.out_lengths && a.workspace, "%s: null pointer", a.fn);
+  if (int rc = pointers()) return rc;
+  const BeamLayout lay = beam_layout(a.B, a.k, a.D, a.L, tables);
+  GLASS_CHECK_ARG(a.workspace_bytes >= (int64_t)lay.total, "%s: workspace too small (%lld < %lld bytes)", a.fn,
+                  (long long)a.workspace_bytes, (long long)lay.total);
+  DecParams p = dec_params(a.x, a.xproj, a.w, a.B * a.k, a.T, a.C, a.L);
+  const BeamCarved c = beam_carve(a.workspace, lay, tables, a.k, a.L, a.eos, p);
+  hipError_t e = hipMemsetAsync(p.h0, 0, (size_t)a.B * a.k * a.D * sizeof(float), a.stream);  // initial state h = 0
+  if (e != hipSuccess) { glass_set_error("%s: memset: %s", a.fn, hipGetErrorString(e)); return GLASS_EHIP; }
+  auto step = make_step(p, c);
+  step(-1);                                                                       // attention for step 0
+  for (int t = 0; t < a.L; ++t) {
+    dec_gru_step(p, p.h0, p.h1, a.stream);
+    step(t);
+  }
+  GLASS_CHECK_LAUNCH(a.fn);
+  final(c);
+  GLASS_CHECK_LAUNCH(final_fn);
+  return GLASS_OK;
 }
 
 // step == -1: only the attention part with h = 0, y = 0 ([GO]) -> inp rows of step 0; step >= 0: fc + log-softmax + running
@@ -191,38 +248,27 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(BeamParams bp, int C
 
 extern "C" int64_t glass_beam_search_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
   (void)T; (void)C;
-  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
-  return (int64_t)beam_layout(B, k, D, max_len).end;
+  return (int64_t)beam_layout(B, k, D, max_len, BEAM_PLAIN).total;
 }
 
 extern "C" int glass_beam_search(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
                                  int C, int max_len, int eos, int* out_symbols, float* out_scores, int* out_lengths,
                                  float* out_path_probs, void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
-  if (int rc = search_limits("glass_beam_search", true, B, k, T, D, C, max_len)) return rc;
-  if (B == 0) return GLASS_OK;
-  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && workspace, "glass_beam_search: null pointer");
-  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_workspace_bytes(B, k, T, D, C, max_len),
-                  "glass_beam_search: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                  (long long)glass_beam_search_workspace_bytes(B, k, T, D, C, max_len));
-  hipStream_t s = (hipStream_t)stream;
-  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
-  const BeamParams bp = beam_carve(workspace, beam_layout(B, k, D, max_len), k, max_len, eos, p);
-  float *hsel = p.h0, *hraw = p.h1;
-  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("glass_beam_search: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
-  const dim3 gb(B);
-  auto beam_step = [&](int step) {
-    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL(beam_step_kernel<decltype(kb)::value>, gb, dim3(256), 0, s, p, bp, hraw, step); });
-  };
-  beam_step(-1);                                                                  // attention for step 0
-  for (int step = 0; step < max_len; ++step) {
-    dec_gru_step(p, hsel, hraw, s);
-    beam_step(step);
-  }
-  GLASS_CHECK_LAUNCH("glass_beam_search");
-  hipLaunchKernelGGL(beam_backtrack_kernel, gb, dim3(64), 0, s, bp, C, out_symbols, out_scores, out_lengths, out_path_probs);
-  GLASS_CHECK_LAUNCH("glass_beam_search(backtrack)");
-  return GLASS_OK;
+  const SearchArgs a = {"glass_beam_search", x, xproj, w, B, k, T, D, C, max_len, eos, out_symbols, out_scores, out_lengths,
+                        out_path_probs, workspace, workspace_bytes, (hipStream_t)stream};
+  return run_beam_search(
+      a, BEAM_PLAIN, "glass_beam_search(backtrack)", no_check, no_check,
+      [&](const DecParams& p, const BeamCarved& c) {
+        return [&](int step) {
+          with_row_block(a.k, [&](auto kb) {
+            hipLaunchKernelGGL(beam_step_kernel<decltype(kb)::value>, dim3(a.B), dim3(256), 0, a.stream, p, c.bp, p.h1, step);
+          });
+        };
+      },
+      [&](const BeamCarved& c) {
+        hipLaunchKernelGGL(beam_backtrack_kernel, dim3(a.B), dim3(64), 0, a.stream, c.bp, C, out_symbols, out_scores, out_lengths,
+                           out_path_probs);
+      });
 }
 
 // ================================================================== forced decoding (AttentionRecognitionHead.forward)
@@ -335,11 +381,17 @@ __global__ __launch_bounds__(256) void forced_step_kernel(DecParams p, ForcedPar
   rows_attend<KB>(p, b, n, row0, u, h, sproj, energy, ysel);
 }
 
+// the workspace as byte offsets and its size, for glass_forced_decode_workspace_bytes and the entry point alike
+struct ForcedLayout { size_t h0, h1, inp, elen, bad, total; };
+static ForcedLayout forced_layout(int B, int n, int D, int L) {
+  if (B <= 0 || n <= 0 || D <= 0 || L <= 0) return {};
+  const size_t rows = (size_t)B * n, state = rows * D * sizeof(float);
+  return {0, state, 2 * state, 4 * state, 4 * state + rows * sizeof(int), 4 * state + 2 * rows * sizeof(int)};
+}
+
 extern "C" int64_t glass_forced_decode_workspace_bytes(int B, int n, int T, int D, int C, int max_len) {
   (void)T; (void)C;
-  if (B <= 0 || n <= 0 || D <= 0 || max_len <= 0) return 0;
-  const size_t rows = (size_t)B * n;
-  return (int64_t)(rows * D * 4 * sizeof(float) + rows * 2 * sizeof(int));
+  return (int64_t)forced_layout(B, n, D, max_len).total;
 }
 
 extern "C" int glass_forced_decode(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T, int D,
@@ -350,21 +402,19 @@ extern "C" int glass_forced_decode(const float* x, const float* xproj, const gla
   if (B == 0) return GLASS_OK;
   GLASS_CHECK_ARG(x && xproj && w && targets && out_step_logp && out_scores && out_lengths && workspace,
                   "glass_forced_decode: null pointer");
-  GLASS_CHECK_ARG(workspace_bytes >= glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len),
-                  "glass_forced_decode: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                  (long long)glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len));
+  const ForcedLayout lay = forced_layout(B, n, D, max_len);
+  GLASS_CHECK_ARG(workspace_bytes >= (int64_t)lay.total, "glass_forced_decode: workspace too small (%lld < %lld bytes)",
+                  (long long)workspace_bytes, (long long)lay.total);
   hipStream_t s = (hipStream_t)stream;
-  const size_t rows = (size_t)B * n;
-  DecParams p = dec_params(x, xproj, w, (int)rows, T, C, max_len);
-  float* ws = static_cast<float*>(workspace);
-  p.h0 = ws; p.h1 = ws + rows * D; p.inp = ws + rows * D * 2;
+  DecParams p = dec_params(x, xproj, w, B * n, T, C, max_len);
+  char* ws = static_cast<char*>(workspace);
+  p.h0 = reinterpret_cast<float*>(ws + lay.h0); p.h1 = reinterpret_cast<float*>(ws + lay.h1); p.inp = reinterpret_cast<float*>(ws + lay.inp);
   ForcedParams fp;
   fp.targets = targets; fp.lengths = lengths; fp.step_logp = out_step_logp; fp.scores = out_scores; fp.out_len = out_lengths;
   fp.probs = out_probs; fp.logits = out_logits;
-  fp.elen = reinterpret_cast<int*>(ws + rows * D * 4);
-  fp.bad = fp.elen + rows;
+  fp.elen = reinterpret_cast<int*>(ws + lay.elen); fp.bad = reinterpret_cast<int*>(ws + lay.bad);
   fp.n = n; fp.L = max_len; fp.eos = eos;
-  hipError_t e = hipMemsetAsync(p.h0, 0, rows * D * sizeof(float), s);           // initial state h = 0
+  hipError_t e = hipMemsetAsync(p.h0, 0, lay.h1 - lay.h0, s);                      // initial state h = 0
   if (e != hipSuccess) { glass_set_error("glass_forced_decode: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
   const dim3 gb(B);
   float* hb[2] = {p.h0, p.h1};
@@ -516,12 +566,13 @@ struct Merged : CP {
 };
 
 // beam_step_kernel with the mask of a constraint CP (LexParams: the trie, DfaParams: the automaton, WdfaParams: the weighted
-// automaton, whose extra work is all under `if constexpr (CP::weighted)`: the other two kernels are what they were).  Thread u owns class u:
-// its k mask words or table entries (one per beam) are loaded once per step into the bit set `allow`; the k node ids live in
-// LDS.  After the selection, thread j moves slot j to its child node / target state.
+// automaton, whose extra work is all under `if constexpr (CP::weighted)`: the other two kernels are what they were).  Thread u
+// owns class u: its k mask words or table entries (one per beam) are loaded once per step into the bit set `allow`; the k
+// node ids live in LDS.  After the selection, thread j moves slot j to its child node / target state.
 // MERGE (CP = Merged<...>): between the running scores and the top-k, the candidates of one beam whose classes share a fold
 // symbol become ONE candidate - the group's arg-max class (ties: the lowest) carries the log of the group's summed mass, the
-// other members lose their `allow` bit; the merged scores pass through sproj (idle at that point), so cand needs no second copy.  All of it is under `if constexpr (MERGE)`: the unmerged kernels are the code they were.
+// other members lose their `allow` bit; the merged scores pass through sproj (idle at that point), so cand needs no second
+// copy.  All of it is under `if constexpr (MERGE)`: the unmerged kernels are the code they were.
 template <int KB, class CP, bool MERGE = false>
 __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams bp, CP lp, const float* __restrict__ hraw,
                                                        int step) {
@@ -719,13 +770,20 @@ __global__ __launch_bounds__(256) void con_step_kernel(DecParams p, BeamParams b
   rows_attend<KB>(p, b, k, row0, u, h, sproj, energy, ysel);
 }
 
+// what con_final_kernel reads of a constraint: the node table and the tag of a node (the trie's node_word, an automaton's accept)
+struct FinalParams {
+  const int* nd;                    // workspace [B][L][k]
+  const int* tag;                   // [N]
+  int N;
+};
+
 // The k best completed entries of one item, one wavefront per item: an entry (t, slot) is completed when its symbol is <eos>
 // and its score finite; order = score descending, then flat index t*k + slot ascending (t, then slot).  Lane l owns the
 // entries l + 64 i; k rounds of the wavefront arg-max, then lane r walks result r back through the predecessor table.
 // W (the weighted search): the entries are ranked by their fused scores `fused` [B][L][k], which go to out_sc; the model scores
 // (bp.sc) go to out_model and, as without W, make the path rows.
 template <bool W>
-__global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams lp, int C, int* __restrict__ out_sym,
+__global__ __launch_bounds__(64) void con_final_kernel(BeamParams bp, FinalParams fp, int C, int* __restrict__ out_sym,
                                                        float* __restrict__ out_sc, int* __restrict__ out_len,
                                                        int* __restrict__ out_word, float* __restrict__ out_path,
                                                        const float* __restrict__ fused, float* __restrict__ out_model) {
@@ -739,7 +797,7 @@ __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams 
     sc[i] = bp.sc[(long)b * n + i];
     pr[i] = bp.pr[(long)b * n + i];
     sy[i] = bp.sy[(long)b * n + i];
-    nd[i] = lp.nd[(long)b * n + i];
+    nd[i] = fp.nd[(long)b * n + i];
     if constexpr (W) fu[i] = fused[(long)b * n + i];
   }
   __syncthreads();
@@ -783,7 +841,7 @@ __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams 
         out_sc[row] = sc[e];
       }
       out_len[row] = t0 + 1;
-      out_word[row] = (node >= 0 && node < lp.N) ? lp.node_word[node] : -1;
+      out_word[row] = (node >= 0 && node < fp.N) ? fp.tag[node] : -1;
       for (int t = L - 1; t > t0; --t) os[t] = bp.eos;
       for (int t = t0; t >= 0; --t) {
         os[t] = sy[t * k + slot];
@@ -805,10 +863,66 @@ __global__ __launch_bounds__(64) void lex_final_kernel(BeamParams bp, LexParams 
   }
 }
 
+// ---- host side of the constrained searches
+// the fold groups of a merged search, checked as far as the host can without reading device memory
+struct FoldGroups { const int* start; const int* cls; int n; };
+static int merged_limits(const char* fn, const FoldGroups& g, int C) {
+  GLASS_CHECK_ARG(g.start && g.cls, "%s: null group array", fn);
+  GLASS_CHECK_ARG(g.n >= 1 && g.n <= C, "%s: needs 1<=n_group_cls<=C (got n_group_cls=%d C=%d)", fn, g.n, C);
+  return GLASS_OK;
+}
+static int automaton_limits(const char* fn, int N, int S, int F) {
+  GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256, "%s: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)",
+                  fn, N, S, F);
+  return GLASS_OK;
+}
+
+// step(int) of a search under constraint cp: con_step_kernel<KB, CP>, or with fold groups con_step_kernel<KB, Merged<CP>, true>.
+// G = const FoldGroups* (null = unmerged), or std::nullptr_t for a constraint that is never merged (the trie), whose merged
+// kernels then do not exist.
+template <class CP, class G>
+static auto con_stepper(const SearchArgs& a, const DecParams& p, const BeamParams& bp, const CP& cp, G groups) {
+  Merged<CP> mp = {};                                                              // group_start stays null: unmerged
+  static_cast<CP&>(mp) = cp;
+  if constexpr (!std::is_null_pointer_v<G>)
+    if (groups != nullptr) { mp.group_start = groups->start; mp.group_cls = groups->cls; mp.n_group_cls = groups->n; }
+  return [&a, &p, &bp, mp](int step) {
+    with_row_block(a.k, [&](auto kb) {
+      constexpr int KB = decltype(kb)::value;
+      const dim3 gb(a.B), tb(256);
+      if constexpr (!std::is_null_pointer_v<G>) {
+        if (mp.group_start != nullptr) {
+          hipLaunchKernelGGL((con_step_kernel<KB, Merged<CP>, true>), gb, tb, 0, a.stream, p, bp, mp, p.h1, step);
+          return;
+        }
+      }
+      hipLaunchKernelGGL((con_step_kernel<KB, CP>), gb, tb, 0, a.stream, p, bp, static_cast<const CP&>(mp), p.h1, step);
+    });
+  };
+}
+
+// run_beam_search for constraint cp (its workspace tables are set here): `tag` [N] = what out_tags reports of a hypothesis's
+// last node; out_model = the weighted search's model scores, else null
+template <class CP, class G, class Limits, class Pointers>
+static int con_search(const SearchArgs& a, const char* final_fn, CP cp, G groups, const int* tag, int* out_tags, float* out_model,
+                      Limits limits, Pointers pointers) {
+  return run_beam_search(
+      a, CP::weighted ? BEAM_WEIGHTED : BEAM_NODES, final_fn, limits, pointers,
+      [&](const DecParams& p, const BeamCarved& c) {
+        cp.nd = c.nd;
+        if constexpr (CP::weighted) { cp.wa = c.wa; cp.fu = c.fu; }
+        return con_stepper(a, p, c.bp, cp, groups);
+      },
+      [&](const BeamCarved& c) {
+        const FinalParams fin = {c.nd, tag, cp.N};
+        hipLaunchKernelGGL(con_final_kernel<CP::weighted>, dim3(a.B), dim3(64), 0, a.stream, c.bp, fin, a.C, a.out_symbols,
+                           a.out_scores, a.out_lengths, out_tags, a.out_path, (const float*)c.fu, out_model);
+      });
+}
+
 extern "C" int64_t glass_beam_search_lexicon_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
   (void)T; (void)C;
-  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
-  return (int64_t)(beam_layout(B, k, D, max_len).end + (size_t)B * max_len * k * sizeof(int));
+  return (int64_t)beam_layout(B, k, D, max_len, BEAM_NODES).total;
 }
 
 extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
@@ -817,111 +931,53 @@ extern "C" int glass_beam_search_lexicon(const float* x, const float* xproj, con
                                          const int* item_segment, int* out_symbols, float* out_scores, int* out_lengths,
                                          int* out_words, float* out_path_probs, void* workspace, int64_t workspace_bytes,
                                          glass_stream_t stream) {
-  if (int rc = search_limits("glass_beam_search_lexicon", true, B, k, T, D, C, max_len)) return rc;
-  GLASS_CHECK_ARG(N >= 1 && S >= 1 && F >= 1 && F <= 256, "glass_beam_search_lexicon: needs N>=1, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)",
-                  N, S, F);
-  if (B == 0) return GLASS_OK;
-  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && out_words && workspace,
-                  "glass_beam_search_lexicon: null pointer");
-  GLASS_CHECK_ARG(child_mask && child_base && node_word && seg_root && fold && item_segment,
-                  "glass_beam_search_lexicon: null trie array");
-  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len),
-                  "glass_beam_search_lexicon: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes,
-                  (long long)glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len));
-  hipStream_t s = (hipStream_t)stream;
-  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
-  const BeamLayout lay = beam_layout(B, k, D, max_len);
-  const BeamParams bp = beam_carve(workspace, lay, k, max_len, eos, p);
-  float *hsel = p.h0, *hraw = p.h1;
+  const SearchArgs a = {"glass_beam_search_lexicon", x, xproj, w, B, k, T, D, C, max_len, eos, out_symbols, out_scores, out_lengths,
+                        out_path_probs, workspace, workspace_bytes, (hipStream_t)stream};
   LexParams lp;
   lp.child_mask = child_mask; lp.child_base = child_base; lp.node_word = node_word; lp.seg_root = seg_root; lp.fold = fold;
-  lp.item_segment = item_segment; lp.nd = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.end);
+  lp.item_segment = item_segment; lp.nd = nullptr;
   lp.N = N; lp.S = S; lp.F = F; lp.MW = (F + 31) / 32;
-  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("glass_beam_search_lexicon: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
-  const dim3 gb(B);
-  auto lex_step = [&](int step) {
-    with_row_block(k, [&](auto kb) { hipLaunchKernelGGL((con_step_kernel<decltype(kb)::value, LexParams>), gb, dim3(256), 0, s, p, bp, lp, hraw, step); });
-  };
-  lex_step(-1);                                                                   // attention for step 0
-  for (int step = 0; step < max_len; ++step) {
-    dec_gru_step(p, hsel, hraw, s);
-    lex_step(step);
-  }
-  GLASS_CHECK_LAUNCH("glass_beam_search_lexicon");
-  hipLaunchKernelGGL(lex_final_kernel<false>, gb, dim3(64), 0, s, bp, lp, C, out_symbols, out_scores, out_lengths, out_words,
-                     out_path_probs, (const float*)nullptr, (float*)nullptr);
-  GLASS_CHECK_LAUNCH("glass_beam_search_lexicon(final)");
-  return GLASS_OK;
+  return con_search(
+      a, "glass_beam_search_lexicon(final)", lp, nullptr, node_word, out_words, (float*)nullptr,
+      [&] {
+        GLASS_CHECK_ARG(N >= 1 && S >= 1 && F >= 1 && F <= 256, "%s: needs N>=1, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", a.fn, N, S, F);
+        return GLASS_OK;
+      },
+      [&] {
+        GLASS_CHECK_ARG(out_words, "%s: null pointer", a.fn);
+        GLASS_CHECK_ARG(child_mask && child_base && node_word && seg_root && fold && item_segment, "%s: null trie array", a.fn);
+        return GLASS_OK;
+      });
 }
 
 // ================================================================== pattern-constrained beam search (glass_hip_feature_dfa.h)
 // glass_beam_search_lexicon with the trie generalised to a DFA over fold symbols: the same step kernel with DfaParams as its
-// constraint, the same workspace, and lex_final_kernel with `accept` in the place of node_word.
+// constraint, the same workspace, and con_final_kernel with `accept` as the tags.  The merged twin
+// (glass_hip_feature_merged.h) is the same search with MERGE in its step kernel.
 extern "C" int64_t glass_beam_search_dfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
   return glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len);
 }
-
-// the fold groups of a merged search, checked as far as the host can without reading device memory
-struct FoldGroups { const int* start; const int* cls; int n; };
-static int merged_limits(const char* fn, const FoldGroups& g, int C) {
-  GLASS_CHECK_ARG(g.start && g.cls, "%s: null group array", fn);
-  GLASS_CHECK_ARG(g.n >= 1 && g.n <= C, "%s: needs 1<=n_group_cls<=C (got n_group_cls=%d C=%d)", fn, g.n, C);
-  return GLASS_OK;
+extern "C" int64_t glass_beam_search_merged_dfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  return glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, max_len);
 }
 
-// glass_beam_search_dfa (groups == nullptr) and glass_beam_search_merged_dfa; fn = the entry point's name, for the messages
-static int dfa_search(const char* fn, const FoldGroups* groups, const float* x, const float* xproj, const glass_decoder_weights* w,
-                      int B, int k, int T, int D, int C, int max_len, int eos, const int* next, const int* accept, const int* start,
-                      const int* fold, int N, int S, int F, const int* item_pattern, int* out_symbols, float* out_scores,
-                      int* out_lengths, int* out_tags, float* out_path_probs, void* workspace, int64_t workspace_bytes,
-                      glass_stream_t stream) {
-  if (int rc = search_limits(fn, true, B, k, T, D, C, max_len)) return rc;
-  GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256,
-                  "%s: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", fn, N, S, F);
-  if (groups != nullptr)
-    if (int rc = merged_limits(fn, *groups, C)) return rc;
-  if (B == 0) return GLASS_OK;
-  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_lengths && out_tags && workspace,
-                  "%s: null pointer", fn);
-  GLASS_CHECK_ARG(next && accept && start && fold && item_pattern, "%s: null automaton array", fn);
-  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len),
-                  "%s: workspace too small (%lld < %lld bytes)", fn, (long long)workspace_bytes,
-                  (long long)glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len));
-  hipStream_t s = (hipStream_t)stream;
-  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
-  const BeamLayout lay = beam_layout(B, k, D, max_len);
-  const BeamParams bp = beam_carve(workspace, lay, k, max_len, eos, p);
-  float *hsel = p.h0, *hraw = p.h1;
+// glass_beam_search_dfa (groups == nullptr) and glass_beam_search_merged_dfa
+static int dfa_search(const SearchArgs& a, const FoldGroups* groups, const int* next, const int* accept, const int* start,
+                      const int* fold, int N, int S, int F, const int* item_pattern, int* out_tags) {
   DfaParams dp;
-  dp.next = next; dp.accept = accept; dp.start = start; dp.fold = fold; dp.item_segment = item_pattern;
-  dp.nd = reinterpret_cast<int*>(static_cast<char*>(workspace) + lay.end);
+  dp.next = next; dp.accept = accept; dp.start = start; dp.fold = fold; dp.item_segment = item_pattern; dp.nd = nullptr;
   dp.N = N; dp.S = S; dp.F = F;
-  LexParams fin = {};                                                              // what lex_final_kernel reads: nd, N, node_word
-  fin.nd = dp.nd; fin.N = N; fin.node_word = accept;
-  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("%s: memset: %s", fn, hipGetErrorString(e)); return GLASS_EHIP; }
-  const dim3 gb(B);
-  Merged<DfaParams> mp = {};
-  static_cast<DfaParams&>(mp) = dp;
-  if (groups != nullptr) { mp.group_start = groups->start; mp.group_cls = groups->cls; mp.n_group_cls = groups->n; }
-  auto dfa_step = [&](int step) {
-    with_row_block(k, [&](auto kb) {
-      constexpr int KB = decltype(kb)::value;
-      if (groups != nullptr) hipLaunchKernelGGL((con_step_kernel<KB, Merged<DfaParams>, true>), gb, dim3(256), 0, s, p, bp, mp, hraw, step);
-      else hipLaunchKernelGGL((con_step_kernel<KB, DfaParams>), gb, dim3(256), 0, s, p, bp, dp, hraw, step);
-    });
-  };
-  dfa_step(-1);                                                                   // attention for step 0
-  for (int step = 0; step < max_len; ++step) {
-    dec_gru_step(p, hsel, hraw, s);
-    dfa_step(step);
-  }
-  GLASS_CHECK_LAUNCH(fn);
-  hipLaunchKernelGGL(lex_final_kernel<false>, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags,
-                     out_path_probs, (const float*)nullptr, (float*)nullptr);
-  GLASS_CHECK_LAUNCH(fn);
-  return GLASS_OK;
+  return con_search(
+      a, a.fn, dp, groups, accept, out_tags, (float*)nullptr,
+      [&] {
+        if (int rc = automaton_limits(a.fn, N, S, F)) return rc;
+        return groups != nullptr ? merged_limits(a.fn, *groups, a.C) : GLASS_OK;
+      },
+      [&] {
+        GLASS_CHECK_ARG(out_tags, "%s: null pointer", a.fn);
+        GLASS_CHECK_ARG(next && accept && start && fold && item_pattern, "%s: null automaton array", a.fn);
+        return GLASS_OK;
+      });
 }
 
 extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
@@ -929,13 +985,9 @@ extern "C" int glass_beam_search_dfa(const float* x, const float* xproj, const g
                                      const int* fold, int N, int S, int F, const int* item_pattern, int* out_symbols,
                                      float* out_scores, int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
                                      int64_t workspace_bytes, glass_stream_t stream) {
-  return dfa_search("glass_beam_search_dfa", nullptr, x, xproj, w, B, k, T, D, C, max_len, eos, next, accept, start, fold, N, S, F,
-                    item_pattern, out_symbols, out_scores, out_lengths, out_tags, out_path_probs, workspace, workspace_bytes, stream);
-}
-
-// ---- the merged twin (glass_hip_feature_merged.h): the same search with MERGE in its step kernel, the same workspace
-extern "C" int64_t glass_beam_search_merged_dfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
-  return glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len);
+  const SearchArgs a = {"glass_beam_search_dfa", x, xproj, w, B, k, T, D, C, max_len, eos, out_symbols, out_scores, out_lengths,
+                        out_path_probs, workspace, workspace_bytes, (hipStream_t)stream};
+  return dfa_search(a, nullptr, next, accept, start, fold, N, S, F, item_pattern, out_tags);
 }
 
 extern "C" int glass_beam_search_merged_dfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
@@ -944,84 +996,47 @@ extern "C" int glass_beam_search_merged_dfa(const float* x, const float* xproj, 
                                             const int* group_cls, int n_group_cls, int* out_symbols, float* out_scores,
                                             int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
                                             int64_t workspace_bytes, glass_stream_t stream) {
+  const SearchArgs a = {"glass_beam_search_merged_dfa", x, xproj, w, B, k, T, D, C, max_len, eos, out_symbols, out_scores,
+                        out_lengths, out_path_probs, workspace, workspace_bytes, (hipStream_t)stream};
   const FoldGroups groups = {group_start, group_cls, n_group_cls};
-  return dfa_search("glass_beam_search_merged_dfa", &groups, x, xproj, w, B, k, T, D, C, max_len, eos, next, accept, start, fold, N,
-                    S, F, item_pattern, out_symbols, out_scores, out_lengths, out_tags, out_path_probs, workspace, workspace_bytes,
-                    stream);
+  return dfa_search(a, &groups, next, accept, start, fold, N, S, F, item_pattern, out_tags);
 }
 
 // ================================================================== weighted-automaton beam search (glass_hip_feature_wdfa.h)
 // glass_beam_search_dfa with a weight on every transition, stop and start: the same step kernel with WdfaParams as its
-// constraint (two scores per slot, ranked by their fusion), lex_final_kernel<true>.
+// constraint (two scores per slot, ranked by their fusion), con_final_kernel<true>, and the merged twin likewise.
 //   workspace: that of glass_beam_search_dfa | weight sums [B,L,k] | fused scores [B,L,k]
 extern "C" int64_t glass_beam_search_wdfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
-  if (B <= 0 || k <= 0 || D <= 0 || max_len <= 0) return 0;
-  return glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, max_len) + (int64_t)2 * B * max_len * k * (int64_t)sizeof(float);
+  (void)T; (void)C;
+  return (int64_t)beam_layout(B, k, D, max_len, BEAM_WEIGHTED).total;
+}
+extern "C" int64_t glass_beam_search_merged_wdfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
+  return glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len);
 }
 
 // glass_beam_search_wdfa (groups == nullptr) and glass_beam_search_merged_wdfa
-static int wdfa_search(const char* fn, const FoldGroups* groups, const float* x, const float* xproj, const glass_decoder_weights* w,
-                       int B, int k, int T, int D, int C, int max_len, int eos, const glass_wdfa_transition* trans,
-                       const float* final_w, const float* start_w, const int* accept, const int* start, const int* fold, int N, int S,
-                       int F, const int* item_pattern, float weight_scale, int* out_symbols, float* out_scores,
-                       float* out_model_scores, int* out_lengths, int* out_tags, float* out_path_probs, void* workspace,
-                       int64_t workspace_bytes, glass_stream_t stream) {
+static int wdfa_search(const SearchArgs& a, const FoldGroups* groups, const glass_wdfa_transition* trans, const float* final_w,
+                       const float* start_w, const int* accept, const int* start, const int* fold, int N, int S, int F,
+                       const int* item_pattern, float weight_scale, float* out_model_scores, int* out_tags) {
   static_assert(sizeof(glass_wdfa_transition) == 8 && offsetof(glass_wdfa_transition, w) == 4, "one 64-bit load per table entry");
-  if (int rc = search_limits(fn, true, B, k, T, D, C, max_len)) return rc;
-  GLASS_CHECK_ARG(N >= 1 && N < (1 << 24) && S >= 1 && F >= 1 && F <= 256,
-                  "%s: needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=%d S=%d F=%d)", fn, N, S, F);
-  GLASS_CHECK_ARG(weight_scale == weight_scale && weight_scale - weight_scale == 0.f,
-                  "%s: weight_scale must be finite (got %g)", fn, (double)weight_scale);
-  if (groups != nullptr)
-    if (int rc = merged_limits(fn, *groups, C)) return rc;
-  if (B == 0) return GLASS_OK;
-  GLASS_CHECK_ARG(x && xproj && w && out_symbols && out_scores && out_model_scores && out_lengths && out_tags && workspace,
-                  "%s: null pointer", fn);
-  GLASS_CHECK_ARG(trans && final_w && start_w && accept && start && fold && item_pattern,
-                  "%s: null automaton array", fn);
-  GLASS_CHECK_ARG((reinterpret_cast<uintptr_t>(trans) & 7u) == 0, "%s: trans is not 8-byte aligned", fn);
-  GLASS_CHECK_ARG(workspace_bytes >= glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len),
-                  "%s: workspace too small (%lld < %lld bytes)", fn, (long long)workspace_bytes,
-                  (long long)glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len));
-  hipStream_t s = (hipStream_t)stream;
-  DecParams p = dec_params(x, xproj, w, B * k, T, C, max_len);
-  const BeamLayout lay = beam_layout(B, k, D, max_len);
-  const BeamParams bp = beam_carve(workspace, lay, k, max_len, eos, p);
-  float *hsel = p.h0, *hraw = p.h1;
-  const size_t table = (size_t)B * max_len * k * sizeof(float);
-  char* ws = static_cast<char*>(workspace);
   WdfaParams wp;
-  wp.trans = reinterpret_cast<const unsigned long long*>(trans); wp.final_w = final_w; wp.start_w = start_w; wp.accept = accept; wp.start = start;
-  wp.fold = fold; wp.item_segment = item_pattern;
-  wp.nd = reinterpret_cast<int*>(ws + lay.end);
-  wp.wa = reinterpret_cast<float*>(ws + lay.end + table);
-  wp.fu = reinterpret_cast<float*>(ws + lay.end + 2 * table);
+  wp.trans = reinterpret_cast<const unsigned long long*>(trans); wp.final_w = final_w; wp.start_w = start_w; wp.accept = accept;
+  wp.start = start; wp.fold = fold; wp.item_segment = item_pattern; wp.nd = nullptr; wp.wa = nullptr; wp.fu = nullptr;
   wp.scale = weight_scale; wp.N = N; wp.S = S; wp.F = F;
-  LexParams fin = {};                                                              // what lex_final_kernel reads: nd, N, node_word
-  fin.nd = wp.nd; fin.N = N; fin.node_word = accept;
-  hipError_t e = hipMemsetAsync(hsel, 0, (size_t)B * k * D * sizeof(float), s);  // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("%s: memset: %s", fn, hipGetErrorString(e)); return GLASS_EHIP; }
-  const dim3 gb(B);
-  Merged<WdfaParams> mp = {};
-  static_cast<WdfaParams&>(mp) = wp;
-  if (groups != nullptr) { mp.group_start = groups->start; mp.group_cls = groups->cls; mp.n_group_cls = groups->n; }
-  auto wdfa_step = [&](int step) {
-    with_row_block(k, [&](auto kb) {
-      constexpr int KB = decltype(kb)::value;
-      if (groups != nullptr) hipLaunchKernelGGL((con_step_kernel<KB, Merged<WdfaParams>, true>), gb, dim3(256), 0, s, p, bp, mp, hraw, step);
-      else hipLaunchKernelGGL((con_step_kernel<KB, WdfaParams>), gb, dim3(256), 0, s, p, bp, wp, hraw, step);
-    });
-  };
-  wdfa_step(-1);                                                                  // attention for step 0
-  for (int step = 0; step < max_len; ++step) {
-    dec_gru_step(p, hsel, hraw, s);
-    wdfa_step(step);
-  }
-  GLASS_CHECK_LAUNCH(fn);
-  hipLaunchKernelGGL(lex_final_kernel<true>, gb, dim3(64), 0, s, bp, fin, C, out_symbols, out_scores, out_lengths, out_tags,
-                     out_path_probs, (const float*)wp.fu, out_model_scores);
-  GLASS_CHECK_LAUNCH(fn);
-  return GLASS_OK;
+  return con_search(
+      a, a.fn, wp, groups, accept, out_tags, out_model_scores,
+      [&] {
+        if (int rc = automaton_limits(a.fn, N, S, F)) return rc;
+        GLASS_CHECK_ARG(weight_scale == weight_scale && weight_scale - weight_scale == 0.f, "%s: weight_scale must be finite (got %g)",
+                        a.fn, (double)weight_scale);
+        return groups != nullptr ? merged_limits(a.fn, *groups, a.C) : GLASS_OK;
+      },
+      [&] {
+        GLASS_CHECK_ARG(out_model_scores && out_tags, "%s: null pointer", a.fn);
+        GLASS_CHECK_ARG(trans && final_w && start_w && accept && start && fold && item_pattern, "%s: null automaton array", a.fn);
+        GLASS_CHECK_ARG((reinterpret_cast<uintptr_t>(trans) & 7u) == 0, "%s: trans is not 8-byte aligned", a.fn);
+        return GLASS_OK;
+      });
 }
 
 extern "C" int glass_beam_search_wdfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T, int D,
@@ -1030,13 +1045,10 @@ extern "C" int glass_beam_search_wdfa(const float* x, const float* xproj, const 
                                       int F, const int* item_pattern, float weight_scale, int* out_symbols, float* out_scores,
                                       float* out_model_scores, int* out_lengths, int* out_tags, float* out_path_probs,
                                       void* workspace, int64_t workspace_bytes, glass_stream_t stream) {
-  return wdfa_search("glass_beam_search_wdfa", nullptr, x, xproj, w, B, k, T, D, C, max_len, eos, trans, final_w, start_w, accept,
-                     start, fold, N, S, F, item_pattern, weight_scale, out_symbols, out_scores, out_model_scores, out_lengths,
-                     out_tags, out_path_probs, workspace, workspace_bytes, stream);
-}
-
-extern "C" int64_t glass_beam_search_merged_wdfa_workspace_bytes(int B, int k, int T, int D, int C, int max_len) {
-  return glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, max_len);
+  const SearchArgs a = {"glass_beam_search_wdfa", x, xproj, w, B, k, T, D, C, max_len, eos, out_symbols, out_scores, out_lengths,
+                        out_path_probs, workspace, workspace_bytes, (hipStream_t)stream};
+  return wdfa_search(a, nullptr, trans, final_w, start_w, accept, start, fold, N, S, F, item_pattern, weight_scale, out_model_scores,
+                     out_tags);
 }
 
 extern "C" int glass_beam_search_merged_wdfa(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int k, int T,
@@ -1047,8 +1059,9 @@ extern "C" int glass_beam_search_merged_wdfa(const float* x, const float* xproj,
                                              float* out_scores, float* out_model_scores, int* out_lengths, int* out_tags,
                                              float* out_path_probs, void* workspace, int64_t workspace_bytes,
                                              glass_stream_t stream) {
+  const SearchArgs a = {"glass_beam_search_merged_wdfa", x, xproj, w, B, k, T, D, C, max_len, eos, out_symbols, out_scores,
+                        out_lengths, out_path_probs, workspace, workspace_bytes, (hipStream_t)stream};
   const FoldGroups groups = {group_start, group_cls, n_group_cls};
-  return wdfa_search("glass_beam_search_merged_wdfa", &groups, x, xproj, w, B, k, T, D, C, max_len, eos, trans, final_w, start_w,
-                     accept, start, fold, N, S, F, item_pattern, weight_scale, out_symbols, out_scores, out_model_scores,
-                     out_lengths, out_tags, out_path_probs, workspace, workspace_bytes, stream);
+  return wdfa_search(a, &groups, trans, final_w, start_w, accept, start, fold, N, S, F, item_pattern, weight_scale,
+                     out_model_scores, out_tags);
 }

@@ -313,19 +313,14 @@ class ASTER_V2(InferenceModule):
         xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x      # empty batch: empty results
         words = model_scores = None
         from ...evaluation.weighted_pattern import WeightedPattern
-        if isinstance(pattern, WeightedPattern):
-            out = K.beam_search_wdfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
-                                     pattern.tensors, seg, weight_scale=float(weight_scale), path_probs=path_probs,
-                                     merge=bool(merge_case))
-            model_scores, words, out = out[2], out[4], out[:2] + out[3:4] + out[5:]
-        elif pattern is not None:
-            out = K.beam_search_dfa(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
-                                    pattern.tensors, seg, path_probs=path_probs, merge=bool(merge_case))
-            words, out = out[3], out[:3] + out[4:]
-        elif lexicon is not None:
-            out = K.beam_search_lexicon(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos),
-                                        lexicon.tensors, seg, path_probs=path_probs)
-            words, out = out[3], out[:3] + out[4:]
+        if pattern is not None or lexicon is not None:
+            weighted = isinstance(pattern, WeightedPattern)
+            family = "wdfa" if weighted else "dfa" if pattern is not None else "lexicon"
+            res = K.constrained_beam_search(family, x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len,
+                                            int(eos), (pattern if pattern is not None else lexicon).tensors, seg, path_probs,
+                                            bool(merge_case), **({"weight_scale": float(weight_scale)} if weighted else {}))
+            words, model_scores = res.get("tags", res.get("words")), res.get("model_scores")
+            out = (res["symbols"], res["scores"], res["lengths"], res["path"])
         else:
             out = K.beam_search(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos), path_probs=path_probs)
         dist = None

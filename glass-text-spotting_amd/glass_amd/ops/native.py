@@ -16,7 +16,7 @@ import math
 import os
 import struct
 import threading
-from typing import List, NamedTuple, Optional, Sequence, Tuple
+from typing import Callable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -1415,44 +1415,8 @@ def beam_search_lexicon(x: torch.Tensor, xproj: torch.Tensor, weights: dict, bea
     the int F (evaluation.lexicon.LexiconTrie.tensors / .num_fold) - and item_segment int32 [B] on x's device ->
     (symbols int32 [B,k,max_len], scores [B,k], lengths int32 [B,k], words int32 [B,k][, path rows [B,max_len,C]]): the k most
     likely lexicon words of each item's segment, best first.  No host synchronisation; limits are checked by the library."""
-    B, T, D, dev = _search_inputs("beam_search_lexicon", x, xproj)
-    k, C, L = int(beam_width), int(num_classes), int(max_len)
-    F = int(trie["F"])
-    MW = (F + 31) // 32
-    arrays = {n: trie.get(n) for n in ("child_mask", "child_base", "node_word", "seg_root", "fold")}
-    N = S = 0
-    for n, t in arrays.items():
-        if t is None:
-            continue
-        _i32(t, n)
-        if t.device != dev:
-            raise GlassLibraryError(f"beam_search_lexicon: {n} on {t.device}, x on {dev}")
-    if arrays["child_mask"] is not None:
-        cm = arrays["child_mask"]
-        N = int(cm.shape[0])
-        if cm.dim() != 2 or (1 <= F <= 256 and cm.shape[1] != MW):      # (an F outside 1..256 is the library's to refuse)
-            raise GlassLibraryError(f"beam_search_lexicon: child_mask {tuple(cm.shape)} is not [N, MW={MW}] (F={F})")
-        for n in ("child_base", "node_word"):
-            if arrays[n] is not None and tuple(arrays[n].shape) != (N,):
-                raise GlassLibraryError(f"beam_search_lexicon: {n} {tuple(arrays[n].shape)} is not [N={N}]")
-    if arrays["seg_root"] is not None:
-        S = int(arrays["seg_root"].numel())
-    if arrays["fold"] is not None and tuple(arrays["fold"].shape) != (C,):
-        raise GlassLibraryError(f"beam_search_lexicon: fold {tuple(arrays['fold'].shape)} is not [C={C}]")
-    _i32(item_segment, "item_segment")
-    if tuple(item_segment.shape) != (B,) or item_segment.device != dev:
-        raise GlassLibraryError(f"beam_search_lexicon: item_segment {tuple(item_segment.shape)} on {item_segment.device} is not [B={B}] on {dev}")
-    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
-    words = torch.empty_like(lengths)
-    w = _decoder_weights(weights)
-    nbytes = int(lib().glass_beam_search_lexicon_workspace_bytes(B, k, T, D, C, L))
-    ws = _workspace(nbytes, dev)
-    check(lib().glass_beam_search_lexicon(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos),
-                                          _opt(arrays["child_mask"]), _opt(arrays["child_base"]), _opt(arrays["node_word"]),
-                                          _opt(arrays["seg_root"]), _opt(arrays["fold"]), N, S, F, _opt(item_segment),
-                                          _dev(symbols), _dev(scores), _dev(lengths), _dev(words), _opt(path), _dev(ws), nbytes,
-                                          stream_handle()), "glass_beam_search_lexicon")
-    return (symbols, scores, lengths, words, path) if path_probs else (symbols, scores, lengths, words)
+    out = constrained_beam_search("lexicon", x, xproj, weights, beam_width, num_classes, max_len, eos, trie, item_segment, path_probs)
+    return _search_tuple("lexicon", out, path_probs)
 
 
 def check_fold_groups(fold, group_start, group_cls, num_classes: int, num_fold: int, eos: int) -> None:
@@ -1516,6 +1480,106 @@ def _merge_arrays(who: str, tables: dict, arrays: dict, C: int, F: int, eos: int
     return gs, gc, int(gc.numel())
 
 
+class _SearchFamily(NamedTuple):
+    """what one constrained beam search's entry points take next to the arguments of glass_beam_search"""
+    who: str                 # the public wrapper, named in the messages
+    arrays: tuple            # (name, dtype) of the constraint's tensors in ABI order; the first is the table whose rows give N
+    table_dims: Callable     # F -> the table's dimensions after N
+    table_text: str          # [N, ...] as the message of a wrong shape writes it
+    per_node: tuple          # the [N] tensors, in the order they are checked
+    per_segment: tuple       # the [S] tensors; the first gives S
+    item: str                # the int32 [B] segment of every item
+    scalars: tuple           # extra float arguments, after `item` (the group arguments of a merged search follow them)
+    outputs: tuple           # the outputs in ABI (= return) order; `path` follows them
+    entry: str
+    merged_entry: Optional[str]
+
+
+_I, _F = torch.int32, torch.float32
+_SEARCH_FAMILIES = {
+    "lexicon": _SearchFamily(
+        "beam_search_lexicon", (("child_mask", _I), ("child_base", _I), ("node_word", _I), ("seg_root", _I), ("fold", _I)),
+        lambda F: ((F + 31) // 32,), "[N, MW={MW}] (F={F})", ("child_base", "node_word"), ("seg_root",),
+        "item_segment", (), ("symbols", "scores", "lengths", "words"), "glass_beam_search_lexicon", None),
+    "dfa": _SearchFamily(
+        "beam_search_dfa", (("next", _I), ("accept", _I), ("start", _I), ("fold", _I)),
+        lambda F: (F,), "[N, F={F}]", ("accept",), ("start",),
+        "item_pattern", (), ("symbols", "scores", "lengths", "tags"), "glass_beam_search_dfa", "glass_beam_search_merged_dfa"),
+    "wdfa": _SearchFamily(
+        "beam_search_wdfa", (("trans", _I), ("final_w", _F), ("start_w", _F), ("accept", _I), ("start", _I), ("fold", _I)),
+        lambda F: (F, 2), "[N, F={F}, 2]", ("accept", "final_w"), ("start", "start_w"),
+        "item_pattern", ("weight_scale",), ("symbols", "scores", "model_scores", "lengths", "tags"),
+        "glass_beam_search_wdfa", "glass_beam_search_merged_wdfa"),
+}
+
+
+def constrained_beam_search(family: str, x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int,
+                            max_len: int, eos: int, tables: dict, item: torch.Tensor, path_probs: bool = False,
+                            merge: bool = False, **scalars) -> dict:
+    """`beam_search_lexicon`, `beam_search_dfa` and `beam_search_wdfa` (`family` = "lexicon" / "dfa" / "wdfa", its description in
+    _SEARCH_FAMILIES): the checks, the outputs and the one ABI call of all three -> the outputs by name, and "path" (None
+    without `path_probs`)."""
+    fam = _SEARCH_FAMILIES[family]
+    who = fam.who
+    B, T, D, dev = _search_inputs(who, x, xproj)
+    k, C, L = int(beam_width), int(num_classes), int(max_len)
+    F = int(tables["F"])
+    arrays = {n: tables.get(n) for n, _ in fam.arrays}
+    groups = _merge_arrays(who, tables, arrays, C, F, int(eos), dev) if merge else None
+    N = S = 0
+    for n, dtype in fam.arrays:
+        t = arrays[n]
+        if t is None:
+            continue
+        _f32c(t, n) if dtype is _F else _i32(t, n)
+        if t.device != dev:
+            raise GlassLibraryError(f"{who}: {n} on {t.device}, x on {dev}")
+
+    def sized(names, size, letter):
+        for n in names:
+            if arrays[n] is not None and tuple(arrays[n].shape) != (size,):
+                raise GlassLibraryError(f"{who}: {n} {tuple(arrays[n].shape)} is not [{letter}={size}]")
+
+    table = fam.arrays[0][0]
+    if arrays[table] is not None:
+        t = arrays[table]
+        N = int(t.shape[0])
+        dims = fam.table_dims(F)
+        # (an F outside 1..256 is the library's to refuse)
+        if t.dim() != 1 + len(dims) or tuple(t.shape[2:]) != dims[1:] or (1 <= F <= 256 and t.shape[1] != dims[0]):
+            raise GlassLibraryError(f"{who}: {table} {tuple(t.shape)} is not {fam.table_text.format(F=F, MW=(F + 31) // 32)}")
+        sized(fam.per_node, N, "N")
+    if arrays[fam.per_segment[0]] is not None:
+        S = int(arrays[fam.per_segment[0]].numel())
+        sized(fam.per_segment[1:], S, "S")
+    sized(("fold",), C, "C")
+    _i32(item, fam.item)
+    if tuple(item.shape) != (B,) or item.device != dev:
+        raise GlassLibraryError(f"{who}: {fam.item} {tuple(item.shape)} on {item.device} is not [B={B}] on {dev}")
+    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
+    out = {"symbols": symbols, "scores": scores, "lengths": lengths, "path": path}
+    for n in fam.outputs:
+        if n not in out:                                                # model_scores [B,k] float32; words / tags [B,k] int32
+            out[n] = torch.empty_like(scores if n == "model_scores" else lengths)
+    w = _decoder_weights(weights)
+    entry = fam.entry if groups is None else fam.merged_entry
+    nbytes = int(getattr(lib(), entry + "_workspace_bytes")(B, k, T, D, C, L))
+    ws = _workspace(nbytes, dev)
+    args = [_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos)]
+    args += [_opt(arrays[n]) for n, _ in fam.arrays] + [N, S, F, _opt(item)] + [float(scalars[n]) for n in fam.scalars]
+    if groups is not None:
+        args += [_dev(groups[0]), _dev(groups[1]), groups[2]]
+    args += [_dev(out[n]) for n in fam.outputs] + [_opt(out["path"]), _dev(ws), nbytes, stream_handle()]
+    check(getattr(lib(), entry)(*args), entry)
+    return out
+
+
+def _search_tuple(family: str, out: dict, path_probs: bool) -> tuple:
+    """the public return of a constrained search: its outputs in ABI order[, the path rows]"""
+    res = tuple(out[n] for n in _SEARCH_FAMILIES[family].outputs)
+    return res + (out["path"],) if path_probs else res
+
+
 def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
                     eos: int, dfa: dict, item_pattern: torch.Tensor, path_probs: bool = False, merge: bool = False):
     """the beam search constrained by an automaton (glass_beam_search_dfa): as `beam_search_lexicon`, with `dfa` - the device
@@ -1527,52 +1591,8 @@ def beam_search_dfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_wi
     symbol are one candidate per beam; `dfa` then also holds group_start int32 [F+1] and group_cls int32 [n].  Hand-made
     groups (and a hand-made `fold`) may be HOST arrays: they are validated (`check_fold_groups`, ValueError) and uploaded.
     No host synchronisation; limits are checked by the library."""
-    B, T, D, dev = _search_inputs("beam_search_dfa", x, xproj)
-    k, C, L = int(beam_width), int(num_classes), int(max_len)
-    F = int(dfa["F"])
-    arrays = {n: dfa.get(n) for n in ("next", "accept", "start", "fold")}
-    groups = _merge_arrays("beam_search_dfa", dfa, arrays, C, F, int(eos), dev) if merge else None
-    N = S = 0
-    for n, t in arrays.items():
-        if t is None:
-            continue
-        _i32(t, n)
-        if t.device != dev:
-            raise GlassLibraryError(f"beam_search_dfa: {n} on {t.device}, x on {dev}")
-    if arrays["next"] is not None:
-        nx = arrays["next"]
-        N = int(nx.shape[0])
-        if nx.dim() != 2 or (1 <= F <= 256 and nx.shape[1] != F):       # (an F outside 1..256 is the library's to refuse)
-            raise GlassLibraryError(f"beam_search_dfa: next {tuple(nx.shape)} is not [N, F={F}]")
-        if arrays["accept"] is not None and tuple(arrays["accept"].shape) != (N,):
-            raise GlassLibraryError(f"beam_search_dfa: accept {tuple(arrays['accept'].shape)} is not [N={N}]")
-    if arrays["start"] is not None:
-        S = int(arrays["start"].numel())
-    if arrays["fold"] is not None and tuple(arrays["fold"].shape) != (C,):
-        raise GlassLibraryError(f"beam_search_dfa: fold {tuple(arrays['fold'].shape)} is not [C={C}]")
-    _i32(item_pattern, "item_pattern")
-    if tuple(item_pattern.shape) != (B,) or item_pattern.device != dev:
-        raise GlassLibraryError(f"beam_search_dfa: item_pattern {tuple(item_pattern.shape)} on {item_pattern.device} is not [B={B}] on {dev}")
-    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
-    tags = torch.empty_like(lengths)
-    w = _decoder_weights(weights)
-    if groups is not None:
-        nbytes = int(lib().glass_beam_search_merged_dfa_workspace_bytes(B, k, T, D, C, L))
-        ws = _workspace(nbytes, dev)
-        check(lib().glass_beam_search_merged_dfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos),
-                                                 _opt(arrays["next"]), _opt(arrays["accept"]), _opt(arrays["start"]),
-                                                 _opt(arrays["fold"]), N, S, F, _opt(item_pattern), _dev(groups[0]),
-                                                 _dev(groups[1]), groups[2], _dev(symbols), _dev(scores), _dev(lengths),
-                                                 _dev(tags), _opt(path), _dev(ws), nbytes, stream_handle()),
-              "glass_beam_search_merged_dfa")
-        return (symbols, scores, lengths, tags, path) if path_probs else (symbols, scores, lengths, tags)
-    nbytes = int(lib().glass_beam_search_dfa_workspace_bytes(B, k, T, D, C, L))
-    ws = _workspace(nbytes, dev)
-    check(lib().glass_beam_search_dfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _opt(arrays["next"]),
-                                      _opt(arrays["accept"]), _opt(arrays["start"]), _opt(arrays["fold"]), N, S, F,
-                                      _opt(item_pattern), _dev(symbols), _dev(scores), _dev(lengths), _dev(tags), _opt(path),
-                                      _dev(ws), nbytes, stream_handle()), "glass_beam_search_dfa")
-    return (symbols, scores, lengths, tags, path) if path_probs else (symbols, scores, lengths, tags)
+    out = constrained_beam_search("dfa", x, xproj, weights, beam_width, num_classes, max_len, eos, dfa, item_pattern, path_probs, merge)
+    return _search_tuple("dfa", out, path_probs)
 
 
 def beam_search_wdfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_width: int, num_classes: int, max_len: int,
@@ -1585,60 +1605,9 @@ def beam_search_wdfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_w
     ranked by -> (symbols int32 [B,k,max_len], fused scores [B,k], model scores [B,k], lengths int32 [B,k], tags int32 [B,k][,
     path rows [B,max_len,C], made from the model scores]).  `merge`: as in `beam_search_dfa`
     (glass_beam_search_merged_wdfa).  No host synchronisation; limits are checked by the library."""
-    B, T, D, dev = _search_inputs("beam_search_wdfa", x, xproj)
-    k, C, L = int(beam_width), int(num_classes), int(max_len)
-    F = int(wdfa["F"])
-    arrays = {n: wdfa.get(n) for n in ("trans", "final_w", "start_w", "accept", "start", "fold")}
-    groups = _merge_arrays("beam_search_wdfa", wdfa, arrays, C, F, int(eos), dev) if merge else None
-    N = S = 0
-    for n, t in arrays.items():
-        if t is None:
-            continue
-        _f32c(t, n) if n in ("final_w", "start_w") else _i32(t, n)
-        if t.device != dev:
-            raise GlassLibraryError(f"beam_search_wdfa: {n} on {t.device}, x on {dev}")
-    if arrays["trans"] is not None:
-        tr = arrays["trans"]
-        N = int(tr.shape[0])
-        if tr.dim() != 3 or tr.shape[2] != 2 or (1 <= F <= 256 and tr.shape[1] != F):     # (an F outside 1..256 is the library's to refuse)
-            raise GlassLibraryError(f"beam_search_wdfa: trans {tuple(tr.shape)} is not [N, F={F}, 2]")
-        for n in ("accept", "final_w"):
-            if arrays[n] is not None and tuple(arrays[n].shape) != (N,):
-                raise GlassLibraryError(f"beam_search_wdfa: {n} {tuple(arrays[n].shape)} is not [N={N}]")
-    if arrays["start"] is not None:
-        S = int(arrays["start"].numel())
-        if arrays["start_w"] is not None and tuple(arrays["start_w"].shape) != (S,):
-            raise GlassLibraryError(f"beam_search_wdfa: start_w {tuple(arrays['start_w'].shape)} is not [S={S}]")
-    if arrays["fold"] is not None and tuple(arrays["fold"].shape) != (C,):
-        raise GlassLibraryError(f"beam_search_wdfa: fold {tuple(arrays['fold'].shape)} is not [C={C}]")
-    _i32(item_pattern, "item_pattern")
-    if tuple(item_pattern.shape) != (B,) or item_pattern.device != dev:
-        raise GlassLibraryError(f"beam_search_wdfa: item_pattern {tuple(item_pattern.shape)} on {item_pattern.device} is not [B={B}] on {dev}")
-    symbols, scores, lengths, path = _search_outputs(dev, B, k, L, C, torch.int32, path_probs)
-    model_scores = torch.empty_like(scores)
-    tags = torch.empty_like(lengths)
-    w = _decoder_weights(weights)
-    if groups is not None:
-        nbytes = int(lib().glass_beam_search_merged_wdfa_workspace_bytes(B, k, T, D, C, L))
-        ws = _workspace(nbytes, dev)
-        check(lib().glass_beam_search_merged_wdfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos),
-                                                  _opt(arrays["trans"]), _opt(arrays["final_w"]), _opt(arrays["start_w"]),
-                                                  _opt(arrays["accept"]), _opt(arrays["start"]), _opt(arrays["fold"]), N, S, F,
-                                                  _opt(item_pattern), float(weight_scale), _dev(groups[0]), _dev(groups[1]),
-                                                  groups[2], _dev(symbols), _dev(scores), _dev(model_scores), _dev(lengths),
-                                                  _dev(tags), _opt(path), _dev(ws), nbytes, stream_handle()),
-              "glass_beam_search_merged_wdfa")
-        out = (symbols, scores, model_scores, lengths, tags)
-        return out + (path,) if path_probs else out
-    nbytes = int(lib().glass_beam_search_wdfa_workspace_bytes(B, k, T, D, C, L))
-    ws = _workspace(nbytes, dev)
-    check(lib().glass_beam_search_wdfa(_dev(x), _dev(xproj), ctypes.byref(w), B, k, T, D, C, L, int(eos), _opt(arrays["trans"]),
-                                       _opt(arrays["final_w"]), _opt(arrays["start_w"]), _opt(arrays["accept"]),
-                                       _opt(arrays["start"]), _opt(arrays["fold"]), N, S, F, _opt(item_pattern),
-                                       float(weight_scale), _dev(symbols), _dev(scores), _dev(model_scores), _dev(lengths),
-                                       _dev(tags), _opt(path), _dev(ws), nbytes, stream_handle()), "glass_beam_search_wdfa")
-    out = (symbols, scores, model_scores, lengths, tags)
-    return out + (path,) if path_probs else out
+    out = constrained_beam_search("wdfa", x, xproj, weights, beam_width, num_classes, max_len, eos, wdfa, item_pattern, path_probs,
+                                  merge, weight_scale=float(weight_scale))
+    return _search_tuple("wdfa", out, path_probs)
 
 
 def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: torch.Tensor, lengths: Optional[torch.Tensor],

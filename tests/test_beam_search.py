@@ -142,3 +142,117 @@ def test_beam_search_entries_are_declared_and_have_no_cpu_fallback():
     x = torch.zeros((1, 4, 256))
     with pytest.raises(_lib.GlassLibraryError):
         K.beam_search(x, x, {}, 2, 97, 26, 0)
+
+
+# ------------------------------------------------------------------ the host side every beam search shares
+@pytest.mark.parametrize("B,k,L,beam,nodes,weighted", [(3, 5, 26, 66120, 67680, 70800), (1, 16, 64, 77824, 81920, 90112),
+                                                       (1, 1, 1, 4108, 4112, 4120), (0, 5, 26, 0, 0, 0)])
+def test_workspace_bytes_of_every_beam_search(B, k, L, beam, nodes, weighted):
+    """hsel | hraw | inp (2x) | sc | pr | sy | nd | wa | fu: four state blocks of B*k*D*4 bytes and three tables of B*L*k*4
+    bytes, one more table for a node-constrained search, three more for a weighted one; nothing for an empty batch.  The
+    expected sizes are that formula worked out by hand."""
+    from glass_amd import _lib
+    _lib.build_library()
+    lib = _lib.lib()
+    for name, want in (("", beam), ("_lexicon", nodes), ("_dfa", nodes), ("_merged_dfa", nodes), ("_wdfa", weighted),
+                       ("_merged_wdfa", weighted)):
+        assert getattr(lib, f"glass_beam_search{name}_workspace_bytes")(B, k, 32, 256, 97, L) == want, name
+
+
+_PTR = 4096                 # never dereferenced: every refusal comes before the first runtime call
+
+
+def _refusal_call(lib, entry, B=2, k=3, N=4, scale=1.0, n=11, out=_PTR, arr=_PTR, trans=_PTR, ws=1 << 40):
+    """one call of `entry` with T=8, D=256, C=13, max_len=5, S=1, F=11: `out` = its last mandatory output, `arr` = one of its
+    constraint's arrays (forced decoding: the targets), `trans` = the weighted table, n = n_group_cls"""
+    p = _PTR
+    head = [p, p, p, B, k, 8, 256, 13, 5, 1]
+    tail = [None, p, ws, None]
+    fn = getattr(lib, entry)
+    if entry == "glass_beam_search":
+        return fn(*head, p, p, out, *tail)
+    if entry == "glass_forced_decode":
+        return fn(*head, arr, None, p, p, out, None, *tail)
+    if entry == "glass_beam_search_lexicon":
+        return fn(*head, p, p, arr, p, p, N, 1, 11, p, p, p, p, out, *tail)
+    groups = [p, p, n] if "merged" in entry else []
+    if entry.endswith("_wdfa"):
+        return fn(*head, trans, arr, p, p, p, p, N, 1, 11, p, scale, *groups, p, p, p, p, out, *tail)
+    return fn(*head, p, arr, p, p, N, 1, 11, p, *groups, p, p, p, out, *tail)
+
+
+_INF = float("inf")
+_LIMITS = ": needs D=256, 1<=T<=64, 1<=C<=256, 1<=k<=16, k<=C, 1<=max_len<=64, B>=0 (got B=2 k=17 T=8 D=256 C=13 max_len=5)"
+_AUTOMATON = ": needs 1<=N<2^24, S>=1, 1<=F<=256 (got N=0 S=1 F=11)"
+# (entry point, two faults from adjacent stages of the check order, the message of the first - None: B == 0 returns 0)
+_FIRST_REFUSALS = [
+    ("glass_beam_search", dict(k=17, out=None), _LIMITS),
+    ("glass_beam_search", dict(k=17, B=0), ": needs D=256, 1<=T<=64, 1<=C<=256, 1<=k<=16, k<=C, 1<=max_len<=64, B>=0 (got B=0 k=17 T=8 D=256 C=13 max_len=5)"),
+    ("glass_beam_search", dict(B=0, out=None), None),
+    ("glass_beam_search", dict(out=None, ws=16), ": null pointer"),
+    ("glass_forced_decode", dict(k=17, out=None), ": needs D=256, 1<=T<=64, 1<=C<=256, 1<=n<=16, 1<=max_len<=64, B>=0 (got B=2 n=17 T=8 D=256 C=13 max_len=5)"),
+    ("glass_forced_decode", dict(k=17, B=0), ": needs D=256, 1<=T<=64, 1<=C<=256, 1<=n<=16, 1<=max_len<=64, B>=0 (got B=0 n=17 T=8 D=256 C=13 max_len=5)"),
+    ("glass_forced_decode", dict(B=0, out=None), None),
+    ("glass_forced_decode", dict(out=None, ws=16), ": null pointer"),
+    ("glass_forced_decode", dict(arr=None, ws=16), ": null pointer"),
+    ("glass_beam_search", dict(ws=16), ": workspace too small (16 < 24936 bytes)"),
+    ("glass_forced_decode", dict(ws=16), ": workspace too small (16 < 24624 bytes)"),
+    ("glass_beam_search_lexicon", dict(k=17, N=0), _LIMITS),
+    ("glass_beam_search_lexicon", dict(N=0, B=0), ": needs N>=1, S>=1, 1<=F<=256 (got N=0 S=1 F=11)"),
+    ("glass_beam_search_lexicon", dict(B=0, out=None), None),
+    ("glass_beam_search_lexicon", dict(out=None, arr=None), ": null pointer"),
+    ("glass_beam_search_lexicon", dict(arr=None, ws=16), ": null trie array"),
+    ("glass_beam_search_lexicon", dict(ws=16), ": workspace too small (16 < 25056 bytes)"),
+    ("glass_beam_search_dfa", dict(k=17, N=0), _LIMITS),
+    ("glass_beam_search_dfa", dict(N=0, B=0), _AUTOMATON),
+    ("glass_beam_search_dfa", dict(B=0, out=None), None),
+    ("glass_beam_search_dfa", dict(out=None, arr=None), ": null pointer"),
+    ("glass_beam_search_dfa", dict(arr=None, ws=16), ": null automaton array"),
+    ("glass_beam_search_dfa", dict(ws=16), ": workspace too small (16 < 25056 bytes)"),
+    ("glass_beam_search_merged_dfa", dict(k=17, N=0), _LIMITS),
+    ("glass_beam_search_merged_dfa", dict(N=0, B=0), _AUTOMATON),
+    ("glass_beam_search_merged_dfa", dict(N=0, n=0), _AUTOMATON),
+    ("glass_beam_search_merged_dfa", dict(n=0, B=0), ": needs 1<=n_group_cls<=C (got n_group_cls=0 C=13)"),
+    ("glass_beam_search_merged_dfa", dict(B=0, out=None), None),
+    ("glass_beam_search_merged_dfa", dict(out=None, arr=None), ": null pointer"),
+    ("glass_beam_search_merged_dfa", dict(arr=None, ws=16), ": null automaton array"),
+    ("glass_beam_search_merged_dfa", dict(ws=16), ": workspace too small (16 < 25056 bytes)"),
+    ("glass_beam_search_wdfa", dict(k=17, N=0), _LIMITS),
+    ("glass_beam_search_wdfa", dict(N=0, B=0), _AUTOMATON),
+    ("glass_beam_search_wdfa", dict(N=0, scale=_INF), _AUTOMATON),
+    ("glass_beam_search_wdfa", dict(scale=_INF, B=0), ": weight_scale must be finite (got inf)"),
+    ("glass_beam_search_wdfa", dict(B=0, out=None), None),
+    ("glass_beam_search_wdfa", dict(out=None, arr=None), ": null pointer"),
+    ("glass_beam_search_wdfa", dict(arr=None, ws=16), ": null automaton array"),
+    ("glass_beam_search_wdfa", dict(arr=None, trans=4100), ": null automaton array"),
+    ("glass_beam_search_wdfa", dict(trans=4100, ws=16), ": trans is not 8-byte aligned"),
+    ("glass_beam_search_wdfa", dict(ws=16), ": workspace too small (16 < 25296 bytes)"),
+    ("glass_beam_search_merged_wdfa", dict(k=17, N=0), _LIMITS),
+    ("glass_beam_search_merged_wdfa", dict(N=0, B=0), _AUTOMATON),
+    ("glass_beam_search_merged_wdfa", dict(N=0, scale=_INF), _AUTOMATON),
+    ("glass_beam_search_merged_wdfa", dict(scale=_INF, B=0), ": weight_scale must be finite (got inf)"),
+    ("glass_beam_search_merged_wdfa", dict(N=0, n=0), _AUTOMATON),
+    ("glass_beam_search_merged_wdfa", dict(n=0, B=0), ": needs 1<=n_group_cls<=C (got n_group_cls=0 C=13)"),
+    ("glass_beam_search_merged_wdfa", dict(scale=_INF, n=0), ": weight_scale must be finite (got inf)"),
+    ("glass_beam_search_merged_wdfa", dict(B=0, out=None), None),
+    ("glass_beam_search_merged_wdfa", dict(out=None, arr=None), ": null pointer"),
+    ("glass_beam_search_merged_wdfa", dict(arr=None, ws=16), ": null automaton array"),
+    ("glass_beam_search_merged_wdfa", dict(arr=None, trans=4100), ": null automaton array"),
+    ("glass_beam_search_merged_wdfa", dict(trans=4100, ws=16), ": trans is not 8-byte aligned"),
+    ("glass_beam_search_merged_wdfa", dict(ws=16), ": workspace too small (16 < 25296 bytes)"),
+]
+
+
+@pytest.mark.parametrize("entry,faults,message", _FIRST_REFUSALS)
+def test_first_refusal_of_every_search(entry, faults, message):
+    """the order of the host-side checks: the search's limits, the automaton's, weight_scale, the groups', B == 0, null
+    pointers, null arrays and alignment, the workspace.  Every call carries two faults; the earlier stage answers."""
+    from glass_amd import _lib
+    _lib.build_library()
+    lib = _lib.lib()
+    rc = _refusal_call(lib, entry, **faults)
+    if message is None:
+        assert rc == 0
+        return
+    assert rc < 0
+    assert lib.glass_last_error().decode() == entry + message
