@@ -7,5 +7,6 @@ from .text_evaluator import (TextResultWriter, boxes_to_polygons, find_match_wor
 from .driver import inference_on_dataset  # noqa: F401
 from .mask_rings import MaskPolygonizer  # noqa: F401
 from .ring_check import RingChecker  # noqa: F401
+from .ring_simplify import simplify_ring, simplify_rings_host  # noqa: F401
 from .rrc_score import (RRCScorer, ThresholdSweep, include_in_dictionary, include_in_dictionary_transcription, load_gt_zip, method_strings,  # noqa: F401
                         parse_detection_line, parse_gt_line, tally_sample, transcription_match)

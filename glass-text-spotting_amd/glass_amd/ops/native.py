@@ -2225,3 +2225,49 @@ def ring_check(pts: torch.Tensor, ring_off_host):
     check(lib().glass_ring_check(pts.data_ptr(), P, dev_off.data_ptr(), n_rings, dev_task.data_ptr(), n_tasks, verdict.data_ptr(),
                                  area2.data_ptr(), stream_handle()), "glass_ring_check")
     return verdict, area2
+
+
+RING_SIMPLIFY_LDS_POINTS = 4096   # GLASS_RING_SIMPLIFY_LDS_POINTS (include/glass_hip_feature_simplify.h): a ring of at most this many
+                                   # points is staged in LDS, a longer one is read from global memory by the same code
+RING_SIMPLIFY_MAX_COORD = 1 << 20  # |coordinate| up to here keeps every 128-bit comparison exact (the bound of glass_ring_check)
+_RING_SIMPLIFY_STATUS = "1 a coordinate beyond 2^20, 2 an offset that decreases or leaves 0..V, 3 chain stack exhausted"
+
+
+def simplify_rings(xy: torch.Tensor, ring_off: torch.Tensor, tolerance):
+    """Exact Douglas-Peucker simplification of every ring of a call (glass_ring_simplify_mark / glass_ring_simplify_write,
+    csrc/ring_simplify.hip; the statement is glass_amd.evaluation.simplify_ring, equalled vertex for vertex): xy contiguous
+    int32 [V, 2] and ring_off contiguous int32 [R + 1] on the same device, exactly what `mask_rings` / `roi_mask_rings`
+    return; tolerance in pixels, a multiple of 1/4 in [0, 1024] (ValueError otherwise).
+    -> (xy_s int32 [V', 2], ring_off_s int32 [R + 1]) device tensors, a closed ring closed again, an empty ring empty.
+    The host waits once, for the kept total (it sizes xy_s) and the status; a non-zero status raises GlassLibraryError.
+    R == 0 or V == 0 launches nothing."""
+    from ..evaluation.ring_simplify import tolerance_q4
+    q4 = tolerance_q4(tolerance)
+    _typed(xy, torch.int32, "xy")
+    _typed(ring_off, torch.int32, "ring_off")
+    if xy.dim() != 2 or xy.shape[1] != 2:
+        raise GlassLibraryError(f"xy must be [V, 2] (got {tuple(xy.shape)})")
+    if ring_off.dim() != 1 or ring_off.shape[0] < 1 or ring_off.device != xy.device:
+        raise GlassLibraryError(f"ring_off must be [R + 1] on xy's device (got {tuple(ring_off.shape)} on {ring_off.device})")
+    V, R = int(xy.shape[0]), int(ring_off.shape[0]) - 1
+    dev = xy.device
+    if R == 0 or V == 0:
+        return torch.empty((0, 2), dtype=torch.int32, device=dev), torch.zeros((R + 1,), dtype=torch.int32, device=dev)
+    L_ = lib()
+    st = stream_handle()
+    ws_bytes = int(L_.glass_ring_simplify_workspace_bytes(V, R))
+    if ws_bytes < 0:
+        raise GlassLibraryError(f"glass_ring_simplify_workspace_bytes({V}, {R}) failed ({ws_bytes})")
+    ws = torch.empty((max(ws_bytes, 16) // 8,), dtype=torch.int64, device=dev)
+    meta = torch.empty((R + 2,), dtype=torch.int32, device=dev)        # ring_off_s [R + 1] | status
+    status = meta.data_ptr() + 4 * (R + 1)
+    check(L_.glass_ring_simplify_mark(xy.data_ptr(), V, ring_off.data_ptr(), R, q4, ws.data_ptr(), ws_bytes, meta.data_ptr(), status,
+                                      st), "glass_ring_simplify_mark")
+    total, code = (int(v) for v in meta[R:].cpu())                     # the host waits: the kept total sizes xy_s
+    if code != 0:
+        raise GlassLibraryError(f"glass_ring_simplify_mark: status {code} ({_RING_SIMPLIFY_STATUS})")
+    xy_s = torch.empty((total, 2), dtype=torch.int32, device=dev)
+    if total:
+        check(L_.glass_ring_simplify_write(xy.data_ptr(), V, ring_off.data_ptr(), R, ws.data_ptr(), ws_bytes, meta.data_ptr(),
+                                           xy_s.data_ptr(), total, st), "glass_ring_simplify_write")
+    return xy_s, meta[:R + 1]
