@@ -79,9 +79,13 @@ __global__ __launch_bounds__(256) void dec_fc_att_kernel(DecParams p, const floa
       }
       wave_argmax_first(best, besti);
       if (lane == 0) {
-        ycur[r] = besti;
-        p.yprev[r0 + r] = besti;
-        p.pred[(long)(r0 + r) * p.max_len + step] = besti;
+        // a NaN or +inf logit makes every probability NaN, no lane offers an index and besti is still the sentinel: the
+        // symbol indexes the embedding table below and in the next step, so it is bound to [0, C) (the sentinel becomes
+        // C - 1, the symbol the persistent kernel feeds); a finite row's arg-max is in range and passes unchanged
+        const int y = min(max(besti, 0), C - 1);
+        ycur[r] = y;
+        p.yprev[r0 + r] = y;
+        p.pred[(long)(r0 + r) * p.max_len + step] = y;
       }
     }
     __syncthreads();

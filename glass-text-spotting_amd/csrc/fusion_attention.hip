@@ -63,7 +63,7 @@ __global__ __launch_bounds__(256) void gc_attention_kernel(float* __restrict__ x
   {
     float c0 = 0.f, c1 = 0.f;
     const int h0 = tid >> 6, h1 = 4 + (tid >> 6);
-    constexpr int GC_U3 = 16;                                   // 32 independent loads per thread in flight; same summation order
+    constexpr int GC_U3 = 16;                                   // 32 independent loads per thread in flight
     for (int pos0 = 0; pos0 < GC_HW; pos0 += GC_U3) {
       float v0[GC_U3], v1[GC_U3];
 #pragma unroll
@@ -71,11 +71,24 @@ __global__ __launch_bounds__(256) void gc_attention_kernel(float* __restrict__ x
         v0[i] = x[(long)(pos0 + i) * GC_C + tid];
         v1[i] = x[(long)(pos0 + i) * GC_C + 256 + tid];
       }
+      // the 16 products of a trip are summed as a tree and join the running sum once: 256 dependent additions drift when the
+      // terms are alike (a head with a uniform softmax sums 256 x v/256: 6e-6 on the output, six times the error of a plain
+      // fp32 evaluation - tests/test_gpu_recognition_edges.py), 16 additions of 16-term trees do not
 #pragma unroll
-      for (int i = 0; i < GC_U3; ++i) {
-        c0 += v0[i] * prob[h0][pos0 + i];
-        c1 += v1[i] * prob[h1][pos0 + i];
+      for (int i = 0; i < GC_U3; i += 2) {
+        v0[i] = __fmaf_rn(v0[i + 1], prob[h0][pos0 + i + 1], v0[i] * prob[h0][pos0 + i]);
+        v1[i] = __fmaf_rn(v1[i + 1], prob[h1][pos0 + i + 1], v1[i] * prob[h1][pos0 + i]);
       }
+#pragma unroll
+      for (int s = 2; s < GC_U3; s *= 2) {
+#pragma unroll
+        for (int i = 0; i < GC_U3; i += 2 * s) {
+          v0[i] += v0[i + s];
+          v1[i] += v1[i + s];
+        }
+      }
+      c0 += v0[0];
+      c1 += v1[0];
     }
     ctx[tid] = c0;
     ctx[256 + tid] = c1;

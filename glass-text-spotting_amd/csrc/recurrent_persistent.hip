@@ -547,9 +547,12 @@ __global__ __launch_bounds__(PD_THREADS) void decode_persistent_kernel(PdParams 
         }
         wave_argmax_first(best, besti);
         if (lane == 0) {
-          if (roi_ok) p.pred[(long)rr * L + (i - 1)] = besti;
+          // non-finite logits leave besti at the sentinel: bound to [0, C) as dec_fc_att_kernel does, so that both paths record
+          // the symbol that is fed (C - 1)
+          const int y = min(max(besti, 0), C - 1);
+          if (roi_ok) p.pred[(long)rr * L + (i - 1)] = y;
           // the symbol of step i - 1 feeds step i: tagged i + 1 like the context it is consumed with
-          if (i < L) __hip_atomic_store(yg + (i & 1) * PD_RB + j, granule((unsigned)(i + 1), __int_as_float(roi_ok ? besti : 0)),
+          if (i < L) __hip_atomic_store(yg + (i & 1) * PD_RB + j, granule((unsigned)(i + 1), __int_as_float(roi_ok ? y : 0)),
                                         __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
       } else if (lane == 0) {

@@ -492,7 +492,12 @@ int glass_recurrence_test_hook(int64_t spin_limit, int withhold_ticket);
  * [embedding | context]), b_ih [3D], b_hh [3D], fcB [C], temperature (host).
  * out [R,max_len,C] softmax probabilities; pred_scratch [R,max_len] ints; `workspace`: device scratch of
  * >= glass_decode_workspace_bytes().  Requires D == 256, T <= 64, C <= 256.  Two step launches per
- * decoding step are issued by this one call.                                                */
+ * decoding step are issued by this one call.
+ * Non-finite inputs (glass_attention_decode and glass_attention_decode_persistent alike): a NaN or an infinity in the
+ * x / xproj rows of a RoI, or finite values large enough to overflow its logits, give UNSPECIFIED probabilities for that
+ * RoI (and, through the early break, unspecified zero rows for the RoIs of its image); every index the kernels derive
+ * stays in range - the greedy symbol that is fed back and recorded in pred_scratch is bound to [0, C), C - 1 when no
+ * class compares greater - so nothing is read or written out of bounds, and the RoIs of other images are unaffected.  */
 typedef struct glass_decoder_weights {
   const float *sW, *sB, *wW, *wB, *emb, *w_ih, *w_hh, *b_ih, *b_hh, *fcW, *fcB;
   float temperature;
@@ -510,7 +515,8 @@ int glass_attention_decode(const float* x, const float* xproj, const glass_decod
  * tgt_embedding.weight @ W_ih[:, :D]^T + b_ih (the embedding half of the GRU input needs no arithmetic per step; `w->emb`,
  * `w->b_ih` are not read).  Needs D == 256, T <= 32, C <= 128 (glass_decode_persistent_supported); `workspace` (16-byte
  * aligned, >= glass_decode_persistent_workspace_bytes) is zeroed by the call.  Bounded waits: bit 1 of `call_status` (may be
- * null) and of glass_recurrence_status, as for glass_bilstm_recurrence_persistent.  Two launches (decoder, early-break mask). */
+ * null) and of glass_recurrence_status, as for glass_bilstm_recurrence_persistent.  Two launches (decoder, early-break mask).
+ * Non-finite inputs: the contract stated at glass_attention_decode (indices in range, other images' RoIs unaffected). */
 int glass_decode_persistent_supported(int T, int D, int C, int max_len);
 int64_t glass_decode_persistent_workspace_bytes(int R);
 int glass_attention_decode_persistent(const float* x, const float* xproj, const glass_decoder_weights* w, const float* sW_rowmajor,

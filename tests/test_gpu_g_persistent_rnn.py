@@ -167,13 +167,26 @@ def test_decoder_shapes_the_persistent_kernel_does_not_take_run_the_step_kernels
     assert lib().glass_decode_persistent_supported(32, 256, 97, 26) == 1
     assert lib().glass_decode_persistent_supported(40, 256, 97, 26) == 0 and lib().glass_decode_persistent_supported(32, 256, 200, 26) == 0
     from glass_amd.ops import native as K
-    dec, _ = _decoder()
+    dec, sd = _decoder()
     x = torch.randn((6, 40, 256), generator=torch.Generator().manual_seed(5)).to(_dev())
     ri = torch.zeros((6,), dtype=torch.int32, device=_dev())
     xproj = K.linear(x.view(6 * 40, 256), dec.w["xW"], dec.w["xB"]).view(6, 40, 256)
     a = K.attention_decode(x, xproj, dec.w, ri, 1, dec.num_classes, dec.max_word_len, 0, mode=(1, 1))
     b = K.attention_decode(x, xproj, dec.w, ri, 1, dec.num_classes, dec.max_word_len, 0, mode="steps")
     assert torch.equal(a, b)
+    # both sides above are the step kernels: hold the result to the float64 reference as well (tests/recognition_ref.py; the
+    # reference is given the xproj the kernels were given).  Its top-2 gap on these inputs is 4.5e-3 at the closest step, the
+    # fp32 evaluation of its formulas is within 7.8e-7 of it, so the bound is 4 x that = 3.1e-6 (floor 1e-6, never above 1e-4)
+    import recognition_edge_cases as E
+    import recognition_ref as RR
+    W = RR.plain_from_state_dict(sd, "roi_heads.recognizer_head.decoder.recognizer.decoder.")
+    xc, xpc = x.cpu(), xproj.cpu()
+    want = RR.greedy_decode(xc, xpc, W, [0] * 6, dec.max_word_len, 0)
+    assert float(want["gap"][want["live"]].min()) > 1e-4
+    err32 = float((RR.greedy_decode(xc, xpc, W, [0] * 6, dec.max_word_len, 0, dtype=torch.float32)["probs"].double() - want["probs"]).abs().max())
+    err = float((a.cpu().double() - want["probs"]).abs().max())
+    print(f"[parity] T=40 step-kernel fall-back vs float64: {err:.2e}, fp32 formulas vs float64 {err32:.2e}, bound {E.bound(err32, 1e-4):.2e}")
+    assert err <= E.bound(err32, 1e-4)
 
 
 def test_persistent_decoder_honours_the_temperature():
