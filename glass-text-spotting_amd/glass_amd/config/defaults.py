@@ -171,7 +171,13 @@ def add_post_process_config(cfg: CN) -> None:
         "BOX_PX_PADDING": [0, 0, 0, 0], "MIN_BOX_DIMENSION": 2, "MAX_OUTSIDE_BOX_MARGIN_PX": 5,
         "MERGE_IOA_THRESH": 0.3, "OVERLAP_WIDTH_PER_HEIGHT_THRESH": 0.3,
         "PAIRS_HEIGHT_RATIO_THRESH": 0.35, "LOW_CONFIDENCE": 0.01, "VALID_CONFIDENCE": 0.15,
-        "DETECT_THRESHOLD": 0.25, "TEXT_THRESHOLD": 0.25, "MAX_ANGLE_DIFF": 15}})
+        "DETECT_THRESHOLD": 0.25, "TEXT_THRESHOLD": 0.25, "MAX_ANGLE_DIFF": 15,
+        # MI355X build only: False = off, nothing changes; True = the surviving words of every image are grouped into text
+        # lines in reading order on the device, right after the word kernel (ops.native.group_lines; the thresholds below
+        # are those of include/glass_hip_feature_lines.h), and every Instances carries pred_line_ids / pred_line_pos /
+        # pred_reading_rank / pred_line_boxes (glass_amd.postprocess.lines_of gives the lines on the host)
+        "GROUP_LINES": False, "LINE_MAX_ANGLE_DIFF": 15.0, "LINE_MIN_HEIGHT_RATIO": 0.5, "LINE_MAX_OFFSET": 0.5,
+        "LINE_MAX_GAP": 1.0}})
 
 
 def get_glass_cfg(config_path: str = None, opts=None) -> CN:

@@ -2271,3 +2271,41 @@ def simplify_rings(xy: torch.Tensor, ring_off: torch.Tensor, tolerance):
         check(L_.glass_ring_simplify_write(xy.data_ptr(), V, ring_off.data_ptr(), R, ws.data_ptr(), ws_bytes, meta.data_ptr(),
                                            xy_s.data_ptr(), total, st), "glass_ring_simplify_write")
     return xy_s, meta[:R + 1]
+
+
+GROUP_LINES_MAX_K = 1024          # GLASS_GROUP_LINES_MAX_K (include/glass_hip_feature_lines.h) = POSTPROCESS_MAX_K
+
+
+def group_lines(boxes: torch.Tensor, counts: torch.Tensor, max_angle_diff: float = 15.0, min_height_ratio: float = 0.5,
+                max_offset: float = 0.5, max_gap: float = 1.0) -> dict:
+    """The words of every image of a batch grouped into text lines in reading order (glass_group_lines, csrc/line_group.hip;
+    include/glass_hip_feature_lines.h has the contract and glass_amd.postprocess.line_grouping.group_lines_host states it in
+    numpy): boxes contiguous float32 [N, K, 5] and counts contiguous int32 [N] on the same device, K <= GROUP_LINES_MAX_K
+    (ValueError above, like postprocess_words; a count above K is clamped to K, rows beyond the count are never read).
+    -> {"line_id" [N,K], "line_pos" [N,K], "order" [N,K], "line_start" [N,K+1], "line_count" [N] (int32), "line_boxes" float32
+    [N,K,5]} device tensors, padded as the header says.  A threshold that is not finite, negative or out of range is a
+    ValueError before any launch.  Stream-ordered: two launches, no read-back; the workspace is allocated here."""
+    from ..postprocess.line_grouping import check_line_params
+    p = check_line_params(max_angle_diff, min_height_ratio, max_offset, max_gap)
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() != 3 or int(boxes.shape[2]) != 5 or int(boxes.shape[1]) > GROUP_LINES_MAX_K:
+        raise ValueError(f"group_lines: boxes {tuple(getattr(boxes, 'shape', ()))}: needs [N, K, 5] with K <= {GROUP_LINES_MAX_K} "
+                         "words per image")
+    _f32c(boxes, "boxes"); _i32(counts, "counts")
+    N, K, _ = (int(v) for v in boxes.shape)
+    if tuple(counts.shape) != (N,) or counts.device != boxes.device:
+        raise ValueError(f"group_lines: counts {tuple(counts.shape)} on {counts.device}: needs [{N}] on {boxes.device}")
+    dev = boxes.device
+    _dev(boxes, "boxes")
+    line_id, line_pos, order, line_start, line_count, line_boxes = (
+        torch.empty(shape, dtype=dt, device=dev) for shape, dt in (
+            ((N, K), torch.int32), ((N, K), torch.int32), ((N, K), torch.int32), ((N, K + 1), torch.int32), ((N,), torch.int32),
+            ((N, K, 5), torch.float32)))
+    if N:
+        ws_bytes = int(lib().glass_group_lines_workspace_bytes(N, K))
+        ws = _workspace(ws_bytes, dev)                   # needs no initialisation
+        par = (ctypes.c_double * 4)(p["max_angle_diff"], p["min_height_ratio"], p["max_offset"], p["max_gap"])
+        check(lib().glass_group_lines(boxes.data_ptr(), _dev(counts, "counts"), N, K, par, line_id.data_ptr(), line_pos.data_ptr(),
+                                      order.data_ptr(), line_start.data_ptr(), line_boxes.data_ptr(), line_count.data_ptr(),
+                                      _dev(ws), ws_bytes, stream_handle()), "glass_group_lines")
+    return {"line_id": line_id, "line_pos": line_pos, "order": order, "line_start": line_start, "line_boxes": line_boxes,
+            "line_count": line_count}

@@ -99,6 +99,12 @@ class PostProcessorRotatedBoxes:
         assert self.valid_score <= self.detect_threshold, \
             "Valid score threshold must be smaller than the other class thresholds, to prevent word-in-word  cases"
         self.max_angle_diff = pp.MAX_ANGLE_DIFF
+        # line grouping (off by default: no launch, no field); a bad threshold is a ValueError here, not at the first image
+        self.line_params = None
+        if pp.get("GROUP_LINES", False):
+            from .line_grouping import check_line_params
+            self.line_params = check_line_params(pp.LINE_MAX_ANGLE_DIFF, pp.LINE_MIN_HEIGHT_RATIO, pp.LINE_MAX_OFFSET,
+                                                 pp.LINE_MAX_GAP)
 
     # ------------------------------------------------------------------ device path (default)
     text_threshold = None          # set by PostProcessorAcademic
@@ -121,6 +127,16 @@ class PostProcessorRotatedBoxes:
         use_text = text is not None and self.text_threshold is not None
         stop = self.text_encoder.character.index("[s]") if use_text else 1
         out = K.postprocess_words(boxes, scores, counts_dev, text if use_text else None, scale_xy, self._thresholds(), stop)
+        lines = None
+        if self.line_params is not None:       # enqueued behind the word kernel, before the read-back below; adds none
+            lines = K.group_lines(out["boxes"], out["count"], **self.line_params)
+            out.update(lines)
+            # the per-word fields for the whole batch at once (the images below take slices): a word's reading rank is its
+            # line's start plus its position (the inverse of `order`), and it carries its line's box
+            lid, lpos = lines["line_id"].long(), lines["line_pos"].long()
+            row = lid.clamp(min=0)                                      # (-1 from the count on; those columns are not sliced)
+            lrank = lines["line_start"].long().gather(1, row) + lpos
+            lbox = lines["line_boxes"].gather(1, row[:, :, None].expand(-1, -1, 5))
         from ..utils.pipeline import ReadBack, StepOutput
         if use_text:          # one read-back (generator form: utils/pipeline.py) of counts, characters and lengths
             h_count, h_char, h_len = yield ReadBack(out["count"], out["char"], out["text_len"])
@@ -142,6 +158,9 @@ class PostProcessorRotatedBoxes:
                 if t is not None:
                     r.set(name, t[n][src])
             r.pred_polygons = out["polygons"][n, :c]
+            if lines is not None:              # per word, so indexing and filtering an Instances keeps them in step
+                r.pred_line_ids, r.pred_line_pos = lid[n, :c], lpos[n, :c]
+                r.pred_reading_rank, r.pred_line_boxes = lrank[n, :c], lbox[n, :c]
             if use_text:
                 from .post_processor_academic import strip_special
                 r.pred_text_scores = out["text_score"][n, :c]
