@@ -706,7 +706,10 @@ def conv2d_nhwc(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, *, stri
     kernel, "f22r" F(2x2,3x3) on the full tile columns of an odd-width map + the last-column strip).  `f43k`: F(4x4) split-K
     slices (None: the cost model decides, 0: never, else slices or (slices, body)).  plan_conv decides under `routing` (default:
     the Routing stamped on `w` at model load, else the raw-tensor default; `precision` overrides its precision for this call) -
-    nothing process-global is read for a model's layers."""
+    nothing process-global is read for a model's layers.  An empty batch (N = 0) is planned like any other and returns `out`
+    untouched without a launch: an empty tensor has no device address, and the library entries - which do return at once on
+    N = 0 themselves (tests/test_gpu_conv_exact.py calls them so) - refuse null pointers first.  conv1x1_dual_nhwc and
+    local_stem_fused do the same; backbone_stem_supported refuses an empty batch."""
     wt = w.raw if isinstance(w, ConvWeight) else _f32c(w, "w")
     rt = routing if routing is not None else routing_of(w)
     if precision is not None and precision != rt.precision:
@@ -741,6 +744,8 @@ def conv2d_nhwc(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, *, stri
         d, rt, x_dtype=x.dtype, out_dtype=out.dtype, res_dtype=residual.dtype if residual is not None else None, res_mode=res_mode,
         packs=w.packs if isinstance(w, ConvWeight) else None, forced=winograd, f43k=f43k)
     _TLS.last_path = path
+    if N == 0:
+        return out      # an empty batch: nothing to launch, and empty tensors have no device address to hand to the library
     L = lib()
     xt = x
     if cast:
@@ -810,6 +815,8 @@ def conv1x1_dual_nhwc(x1: torch.Tensor, x2: torch.Tensor, w: "ConvWeight", bias:
     out = torch.empty((N, Ho, Wo, Cout), dtype=torch.float32, device=x1.device)
     d = ConvDesc(N, H, W, Cin1, Cout, 1, 1, stride, stride, 0, 0, Ho, Wo, ldx, Cout, 0, 1, relu, 0, 0)
     _TLS.last_path = "pointwise_split"
+    if N == 0:
+        return out      # (as conv2d_nhwc: an empty batch has no device address to hand to the library)
     check(lib().glass_conv1x1_pointwise_split_dual_nhwc(ctypes.byref(d), _dev(x1, "x1"), _dev(x2, "x2"), int(Cin2),
                                                         int(x2.shape[3]), _dev(_packed(w, w.raw, "pws"), "w"), _opt(bias, "bias"),
                                                         _dev(out, "out"), stream_handle()),
@@ -868,8 +875,8 @@ def linear(x: torch.Tensor, w, bias: Optional[torch.Tensor] = None, relu: int = 
     glass_conv2d_nhwc_splitk (conv2d_nhwc routes them)."""
     M, K = x.shape
     y = conv2d_nhwc(x.view(M, 1, 1, K), w if isinstance(w, ConvWeight) else w.view(w.shape[0], 1, 1, K), bias, relu=relu,
-                    out=None if out is None else out.view(M, 1, 1, -1), out_dtype=out_dtype, precision=precision, routing=routing)
-    return y.view(M, -1)
+                    out=None if out is None else out.view(M, 1, 1, out.shape[-1]), out_dtype=out_dtype, precision=precision, routing=routing)
+    return y.view(M, y.shape[-1])       # (no -1: M may be 0)
 
 
 def _raw(w) -> torch.Tensor:
@@ -895,6 +902,8 @@ def local_stem_fused(x: torch.Tensor, w1, b1: torch.Tensor, w2, b2: torch.Tensor
         _f32c(t, n)
     R, H, W, _ = x.shape
     y = torch.empty((R, H // 2, W // 2, 32), dtype=torch.float16 if h16 else torch.float32, device=x.device)
+    if R == 0:
+        return y        # (as conv2d_nhwc)
     fn = lib().glass_local_stem_fused_h16 if h16 else lib().glass_local_stem_fused
     check(fn(_dev(x), _dev(w1), _dev(b1), _dev(w2), _dev(b2), _dev(y), R, H, W, stream_handle()), "glass_local_stem_fused")
     return y
