@@ -177,7 +177,12 @@ def add_post_process_config(cfg: CN) -> None:
         # are those of include/glass_hip_feature_lines.h), and every Instances carries pred_line_ids / pred_line_pos /
         # pred_reading_rank / pred_line_boxes (glass_amd.postprocess.lines_of gives the lines on the host)
         "GROUP_LINES": False, "LINE_MAX_ANGLE_DIFF": 15.0, "LINE_MIN_HEIGHT_RATIO": 0.5, "LINE_MAX_OFFSET": 0.5,
-        "LINE_MAX_GAP": 1.0}})
+        "LINE_MAX_GAP": 1.0,
+        # with GROUP_LINES only (a ValueError without): True = the lines are also ordered column by column and cut into blocks
+        # on the device, right behind the line grouping (ops.native.order_lines; the thresholds are those of
+        # include/glass_hip_feature_layout.h), and every Instances carries pred_page_rank / pred_block_ids / pred_block_boxes
+        # (glass_amd.postprocess.blocks_of and page_text give the blocks and the text on the host)
+        "ORDER_LINES": False, "ORDER_MIN_OVERLAP": 0.1, "BLOCK_MAX_GAP": 0.8, "BLOCK_MIN_HEIGHT_RATIO": 0.7}})
 
 
 def get_glass_cfg(config_path: str = None, opts=None) -> CN:

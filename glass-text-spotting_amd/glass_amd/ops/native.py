@@ -2318,3 +2318,55 @@ def group_lines(boxes: torch.Tensor, counts: torch.Tensor, max_angle_diff: float
                                       _dev(ws), ws_bytes, stream_handle()), "glass_group_lines")
     return {"line_id": line_id, "line_pos": line_pos, "order": order, "line_start": line_start, "line_boxes": line_boxes,
             "line_count": line_count}
+
+
+ORDER_LINES_MAX_K = 1024          # GLASS_ORDER_LINES_MAX_K (include/glass_hip_feature_layout.h) = GROUP_LINES_MAX_K
+
+
+def order_lines(line_boxes: torch.Tensor, line_count: torch.Tensor, line_start: Optional[torch.Tensor] = None,
+                min_overlap: float = 0.1, block_max_gap: float = 0.8, block_min_height_ratio: float = 0.7) -> dict:
+    """The text lines of every image of a batch ordered column by column and cut into blocks (glass_order_lines,
+    csrc/line_order.hip; include/glass_hip_feature_layout.h has the contract and
+    glass_amd.postprocess.line_order.order_lines_host states it in numpy): line_boxes contiguous float32 [N, K, 5] and line_count
+    contiguous int32 [N] on the same device as `group_lines` returns them, K <= ORDER_LINES_MAX_K (ValueError above; a count above
+    K is clamped to K, rows beyond the count are never read), optionally line_start contiguous int32 [N, K + 1].
+    -> {"page_rank" [N,K], "page_order" [N,K], "block_id" [N,K], "block_start" [N,K+1], "block_count" [N], "forced" [N] (int32),
+    "block_boxes" float32 [N,K,5]} and, with line_start, "line_first" int32 [N,K]: device tensors, padded as the header says.
+    A threshold that is not finite or out of range is a ValueError before any launch.  Stream-ordered: four launches, no
+    read-back; the workspace is allocated here."""
+    from ..postprocess.line_order import check_order_params
+    p = check_order_params(min_overlap, block_max_gap, block_min_height_ratio)
+    if (not isinstance(line_boxes, torch.Tensor) or line_boxes.dim() != 3 or int(line_boxes.shape[2]) != 5
+            or int(line_boxes.shape[1]) > ORDER_LINES_MAX_K):
+        raise ValueError(f"order_lines: line_boxes {tuple(getattr(line_boxes, 'shape', ()))}: needs [N, K, 5] with "
+                         f"K <= {ORDER_LINES_MAX_K} lines per image")
+    _f32c(line_boxes, "line_boxes"); _i32(line_count, "line_count")
+    N, K, _ = (int(v) for v in line_boxes.shape)
+    dev = line_boxes.device
+    if tuple(line_count.shape) != (N,) or line_count.device != dev:
+        raise ValueError(f"order_lines: line_count {tuple(line_count.shape)} on {line_count.device}: needs [{N}] on {dev}")
+    if line_start is not None:
+        _i32(line_start, "line_start")
+        if tuple(line_start.shape) != (N, K + 1) or line_start.device != dev:
+            raise ValueError(f"order_lines: line_start {tuple(line_start.shape)} on {line_start.device}: needs [{N}, {K + 1}] on {dev}")
+    _dev(line_boxes, "line_boxes")
+    page_rank, page_order, block_id, block_start, block_count, forced, block_boxes = (
+        torch.empty(shape, dtype=dt, device=dev) for shape, dt in (
+            ((N, K), torch.int32), ((N, K), torch.int32), ((N, K), torch.int32), ((N, K + 1), torch.int32), ((N,), torch.int32),
+            ((N,), torch.int32), ((N, K, 5), torch.float32)))
+    line_first = torch.empty((N, K), dtype=torch.int32, device=dev) if line_start is not None else None
+    if N:
+        ws_bytes = int(lib().glass_order_lines_workspace_bytes(N, K))
+        ws = _workspace(ws_bytes, dev)                   # needs no initialisation
+        par = (ctypes.c_double * 3)(p["min_overlap"], p["block_max_gap"], p["block_min_height_ratio"])
+        check(lib().glass_order_lines(line_boxes.data_ptr(), _dev(line_count, "line_count"),
+                                      _dev(line_start, "line_start") if line_start is not None else None, N, K, par,
+                                      page_rank.data_ptr(), page_order.data_ptr(), block_id.data_ptr(), block_start.data_ptr(),
+                                      block_boxes.data_ptr(), block_count.data_ptr(), forced.data_ptr(),
+                                      line_first.data_ptr() if line_first is not None else None, _dev(ws), ws_bytes,
+                                      stream_handle()), "glass_order_lines")
+    out = {"page_rank": page_rank, "page_order": page_order, "block_id": block_id, "block_start": block_start,
+           "block_boxes": block_boxes, "block_count": block_count, "forced": forced}
+    if line_first is not None:
+        out["line_first"] = line_first
+    return out

@@ -6,7 +6,8 @@ A word is (cx, cy, w, h, a): float32, a in degrees, the convention of `boxes_to_
 first.  u = (cos t, -sin t) with t = a pi / 180 is the word's reading direction, v = (sin t, cos t) its downward direction.
 Words are linked by a symmetric pair rule, the connected components of the links are the lines, words are ordered along their
 line's direction, lines down the page, and every line gets its enclosing rotated box.  Top-to-bottom and no more: two columns
-interleave row by row.
+interleave row by row.  POST_PROCESSING.ORDER_LINES (line_order.py) orders these lines column by column and cuts them into
+blocks; nothing here changes with it.
 """
 from __future__ import annotations
 

@@ -105,6 +105,13 @@ class PostProcessorRotatedBoxes:
             from .line_grouping import check_line_params
             self.line_params = check_line_params(pp.LINE_MAX_ANGLE_DIFF, pp.LINE_MIN_HEIGHT_RATIO, pp.LINE_MAX_OFFSET,
                                                  pp.LINE_MAX_GAP)
+        # page order and blocks on top of the lines (off by default: no launch, no field)
+        self.order_params = None
+        if pp.get("ORDER_LINES", False):
+            if self.line_params is None:
+                raise ValueError("POST_PROCESSING.ORDER_LINES orders the lines that POST_PROCESSING.GROUP_LINES makes: switch it on too")
+            from .line_order import check_order_params
+            self.order_params = check_order_params(pp.ORDER_MIN_OVERLAP, pp.BLOCK_MAX_GAP, pp.BLOCK_MIN_HEIGHT_RATIO)
 
     # ------------------------------------------------------------------ device path (default)
     text_threshold = None          # set by PostProcessorAcademic
@@ -137,6 +144,14 @@ class PostProcessorRotatedBoxes:
             row = lid.clamp(min=0)                                      # (-1 from the count on; those columns are not sliced)
             lrank = lines["line_start"].long().gather(1, row) + lpos
             lbox = lines["line_boxes"].gather(1, row[:, :, None].expand(-1, -1, 5))
+        page = None
+        if lines is not None and self.order_params is not None:        # right behind the line grouping, before the read-back
+            page = K.order_lines(lines["line_boxes"], lines["line_count"], lines["line_start"], **self.order_params)
+            out.update(page)
+            # per word: its page rank is the words ahead of its line plus its position; it carries its block's id and box
+            prank = page["line_first"].long().gather(1, row) + lpos
+            bid = page["block_id"].long().gather(1, row)
+            bbox = page["block_boxes"].gather(1, bid.clamp(min=0)[:, :, None].expand(-1, -1, 5))
         from ..utils.pipeline import ReadBack, StepOutput
         if use_text:          # one read-back (generator form: utils/pipeline.py) of counts, characters and lengths
             h_count, h_char, h_len = yield ReadBack(out["count"], out["char"], out["text_len"])
@@ -161,6 +176,8 @@ class PostProcessorRotatedBoxes:
             if lines is not None:              # per word, so indexing and filtering an Instances keeps them in step
                 r.pred_line_ids, r.pred_line_pos = lid[n, :c], lpos[n, :c]
                 r.pred_reading_rank, r.pred_line_boxes = lrank[n, :c], lbox[n, :c]
+            if page is not None:
+                r.pred_page_rank, r.pred_block_ids, r.pred_block_boxes = prank[n, :c], bid[n, :c], bbox[n, :c]
             if use_text:
                 from .post_processor_academic import strip_special
                 r.pred_text_scores = out["text_score"][n, :c]

@@ -43,7 +43,8 @@ extern "C" {
  *   extent along U, extent along V, atan2(-U_y, U_x) in degrees), rounded to float32 once, at the end.
  * Order of lines: the page frame P_U, P_V is built the same way from all valid words (a fixed-shape tree sum; fallback
  *   (1, 0)); lines go ascending by m.P_V, then m.P_U, then smallest member index, m the unrounded box centre.  This is
- *   top-to-bottom and no more: two columns interleave row by row.
+ *   top-to-bottom and no more: two columns interleave row by row.  (POST_PROCESSING.ORDER_LINES, glass_hip_feature_layout.h,
+ *   orders these lines column by column and cuts them into blocks; nothing here changes with it.)
  *
  * Outputs, every row written up to K whatever the count:
  *   line_id    int32 [N][K]      rank of the word's line, -1 from the count on
