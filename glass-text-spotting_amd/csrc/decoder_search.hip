@@ -6,6 +6,7 @@
 #include <type_traits>
 #include "decoder_common.h"
 #include "glass_hip_ext.h"
+#include "glass_hip_feature_chars.h"
 #include "glass_hip_feature_dfa.h"
 #include "glass_hip_feature_merged.h"
 #include "glass_hip_feature_wdfa.h"
@@ -291,14 +292,23 @@ struct ForcedParams {
   int* bad;                         // workspace [B*n]: 1 = the sequence stopped at a symbol outside [0, C)
   int n, L, eos;
 };
+// what forced_step_kernel<KB, true> (glass_forced_attention) writes besides: a struct of its own and the kernel's LAST argument, so
+// that the ATT = false kernel finds every other argument where it was
+struct ForcedAttention {
+  float* rows;                      // [B][n][L][T], cleared by the host; row t = the weights that made the context of step t
+};
 
 // step == -1: effective lengths from `lengths` or the first <eos>, scores = 0, and the attention part with h = 0, y = 0 ([GO])
 // -> inp rows of step 0; step >= 0: fc + log-softmax of the GRU's output rows -> the records of row `step` (zeros for a
 // sequence that has ended), then - if any sequence goes on - attention with y = targets[step] -> inp rows of step + 1.
 // A symbol is used as an index (embedding row, log-softmax entry) only after the range check of the step -1 launch, which ends a
 // sequence AT the first symbol outside [0, C) with score -inf; the index is clamped once more where it is used.
-template <int KB>
-__global__ __launch_bounds__(256) void forced_step_kernel(DecParams p, ForcedParams fp, const float* __restrict__ hraw, int step) {
+// ATT (glass_forced_attention, glass_hip_feature_chars.h): after the attention part, the weights it left in `energy` go to row
+// step + 1 of every sequence that goes on to that step (one writer per element); all of it is under `if constexpr (ATT)`: the
+// ATT = false kernel is the code it was.
+template <int KB, bool ATT>
+__global__ __launch_bounds__(256) void forced_step_kernel(DecParams p, ForcedParams fp, const float* __restrict__ hraw, int step,
+                                                          ForcedAttention fa) {
   __shared__ __attribute__((aligned(16))) float h[KB][DEC_D];
   __shared__ __attribute__((aligned(16))) float sproj[KB][DEC_D];
   __shared__ float cand[KB][DEC_CMAX];
@@ -379,6 +389,14 @@ __global__ __launch_bounds__(256) void forced_step_kernel(DecParams p, ForcedPar
     __syncthreads();
   }
   rows_attend<KB>(p, b, n, row0, u, h, sproj, energy, ysel);
+  if constexpr (ATT) {
+    __syncthreads();
+    const int T = p.T, at = step + 1;                           // at < L: the launch of step L - 1 has returned above
+    for (int i = u; i < n * T; i += 256) {
+      const int r = i / T, t = i - r * T;
+      if (at < slen[r]) fa.rows[((row0 + r) * L + at) * T + t] = energy[r][t];
+    }
+  }
 }
 
 // the workspace as byte offsets and its size, for glass_forced_decode_workspace_bytes and the entry point alike
@@ -394,16 +412,18 @@ extern "C" int64_t glass_forced_decode_workspace_bytes(int B, int n, int T, int 
   return (int64_t)forced_layout(B, n, D, max_len).total;
 }
 
-extern "C" int glass_forced_decode(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T, int D,
-                                   int C, int max_len, int eos, const int* targets, const int* lengths, float* out_step_logp,
-                                   float* out_scores, int* out_lengths, float* out_probs, float* out_logits, void* workspace,
-                                   int64_t workspace_bytes, glass_stream_t stream) {
-  if (int rc = search_limits("glass_forced_decode", false, B, n, T, D, C, max_len)) return rc;
+// the host side of glass_forced_decode (attention == nullptr: the ATT = false kernels) and of glass_forced_attention (the
+// ATT = true kernels, the rows cleared by a memset first); fn = the entry's name, for the messages
+static int run_forced(const char* fn, bool att, const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n,
+                      int T, int D, int C, int max_len, int eos, const int* targets, const int* lengths, float* out_step_logp,
+                      float* out_scores, int* out_lengths, float* out_probs, float* out_logits, float* attention, void* workspace,
+                      int64_t workspace_bytes, glass_stream_t stream) {
+  if (int rc = search_limits(fn, false, B, n, T, D, C, max_len)) return rc;
   if (B == 0) return GLASS_OK;
-  GLASS_CHECK_ARG(x && xproj && w && targets && out_step_logp && out_scores && out_lengths && workspace,
-                  "glass_forced_decode: null pointer");
+  GLASS_CHECK_ARG(x && xproj && w && targets && out_step_logp && out_scores && out_lengths && workspace && (!att || attention),
+                  "%s: null pointer", fn);
   const ForcedLayout lay = forced_layout(B, n, D, max_len);
-  GLASS_CHECK_ARG(workspace_bytes >= (int64_t)lay.total, "glass_forced_decode: workspace too small (%lld < %lld bytes)",
+  GLASS_CHECK_ARG(workspace_bytes >= (int64_t)lay.total, "%s: workspace too small (%lld < %lld bytes)", fn,
                   (long long)workspace_bytes, (long long)lay.total);
   hipStream_t s = (hipStream_t)stream;
   DecParams p = dec_params(x, xproj, w, B * n, T, C, max_len);
@@ -414,20 +434,48 @@ extern "C" int glass_forced_decode(const float* x, const float* xproj, const gla
   fp.probs = out_probs; fp.logits = out_logits;
   fp.elen = reinterpret_cast<int*>(ws + lay.elen); fp.bad = reinterpret_cast<int*>(ws + lay.bad);
   fp.n = n; fp.L = max_len; fp.eos = eos;
+  const ForcedAttention fa = {att ? attention : nullptr};
   hipError_t e = hipMemsetAsync(p.h0, 0, lay.h1 - lay.h0, s);                      // initial state h = 0
-  if (e != hipSuccess) { glass_set_error("glass_forced_decode: memset: %s", hipGetErrorString(e)); return GLASS_EHIP; }
+  if (e == hipSuccess && att) e = hipMemsetAsync(attention, 0, (size_t)B * n * max_len * T * sizeof(float), s);
+  if (e != hipSuccess) { glass_set_error("%s: memset: %s", fn, hipGetErrorString(e)); return GLASS_EHIP; }
   const dim3 gb(B);
   float* hb[2] = {p.h0, p.h1};
   auto forced_step = [&](const float* hraw, int step) {
-    with_row_block(n, [&](auto kb) { hipLaunchKernelGGL(forced_step_kernel<decltype(kb)::value>, gb, dim3(256), 0, s, p, fp, hraw, step); });
+    with_row_block(n, [&](auto kb) {
+      constexpr int KB = decltype(kb)::value;
+      if (att) hipLaunchKernelGGL((forced_step_kernel<KB, true>), gb, dim3(256), 0, s, p, fp, hraw, step, fa);
+      else hipLaunchKernelGGL((forced_step_kernel<KB, false>), gb, dim3(256), 0, s, p, fp, hraw, step, fa);
+    });
   };
   forced_step(hb[0], -1);                                                         // lengths, and the attention for step 0
   for (int step = 0; step < max_len; ++step) {
     dec_gru_step(p, hb[step & 1], hb[(step + 1) & 1], s);
     forced_step(hb[(step + 1) & 1], step);
   }
-  GLASS_CHECK_LAUNCH("glass_forced_decode");
+  GLASS_CHECK_LAUNCH(fn);
   return GLASS_OK;
+}
+
+extern "C" int glass_forced_decode(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T, int D,
+                                   int C, int max_len, int eos, const int* targets, const int* lengths, float* out_step_logp,
+                                   float* out_scores, int* out_lengths, float* out_probs, float* out_logits, void* workspace,
+                                   int64_t workspace_bytes, glass_stream_t stream) {
+  return run_forced("glass_forced_decode", false, x, xproj, w, B, n, T, D, C, max_len, eos, targets, lengths, out_step_logp,
+                    out_scores, out_lengths, out_probs, out_logits, nullptr, workspace, workspace_bytes, stream);
+}
+
+// glass_hip_feature_chars.h: glass_forced_decode, and the attention rows [B][n][L][T] that formed each step's context
+extern "C" int64_t glass_forced_attention_workspace_bytes(int B, int n, int T, int D, int C, int max_len) {
+  return glass_forced_decode_workspace_bytes(B, n, T, D, C, max_len);
+}
+
+extern "C" int glass_forced_attention(const float* x, const float* xproj, const glass_decoder_weights* w, int B, int n, int T,
+                                      int D, int C, int max_len, int eos, const int* targets, const int* lengths,
+                                      float* out_step_logp, float* out_scores, int* out_lengths, float* out_probs,
+                                      float* out_logits, float* out_attention, void* workspace, int64_t workspace_bytes,
+                                      glass_stream_t stream) {
+  return run_forced("glass_forced_attention", true, x, xproj, w, B, n, T, D, C, max_len, eos, targets, lengths, out_step_logp,
+                    out_scores, out_lengths, out_probs, out_logits, out_attention, workspace, workspace_bytes, stream);
 }
 
 // ================================================================== lexicon-constrained beam search (glass_hip_ext.h)

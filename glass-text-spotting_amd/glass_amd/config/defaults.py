@@ -161,6 +161,12 @@ def add_e2e_config(cfg: CN) -> None:
     # (RecognizerRCNNHeadV3.set_pattern(merge_case=True), include/glass_hip_feature_merged.h): k distinct folded strings, and
     # the word score is the probability of the word, not of one casing
     blk["DECODE_MERGE_CASE"] = False
+    # MI355X build only: False = off, no launch and no field is added; True = the head replays the emitted symbols once
+    # (glass_forced_attention; with BEAM_DISTRIBUTIONS the same replay supplies `pred_text_dist`), turns the decoder's attention
+    # rows into spans along the pooled box (glass_char_spans, include/glass_hip_feature_chars.h) and every Instances carries
+    # pred_char_spans / pred_char_centres / pred_char_count / pred_char_monotone / pred_char_frames
+    # (glass_amd.postprocess.char_quads and chars_of give the quads and the characters)
+    blk["CHAR_BOXES"] = False
     cfg.MODEL.merge_from_other_cfg({"ROI_RECOGNIZER_HEAD": blk})
 
 

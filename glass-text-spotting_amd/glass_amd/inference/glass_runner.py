@@ -26,6 +26,11 @@ from ..utils.host import limit_host_threads
 from .tiling import plan_tiles
 
 
+def _char_boxes_on(model) -> bool:
+    """MODEL.ROI_RECOGNIZER_HEAD.CHAR_BOXES of the model's recogniser head (a model without one: off)"""
+    return bool(getattr(getattr(getattr(model, "roi_heads", None), "recognizer_head", None), "char_boxes", False))
+
+
 class GlassRunner:
     def __init__(self, model_path: Optional[str], config_path: Optional[str], opts: List[str] = None, post_process=True,
                  cfg=None, state_dict=None):
@@ -122,6 +127,16 @@ class GlassRunner:
                     # scaled to the original image's pixels (the masks' frame; pred_boxes may be enlarged by the merge step)
                     extra["pred_mask_rois"] = rois
                     extra["pred_mask_boxes"] = self._scaled_boxes(det.boxes, sc)
+                chars = getattr(det, "chars", None)
+                if _char_boxes_on(self.model):
+                    # MODEL.ROI_RECOGNIZER_HEAD.CHAR_BOXES: the (normalised) character rows ride along like the distributions, with
+                    # the boxes the recogniser pooled, scaled to the original image's pixels, as their frame (pred_boxes may be
+                    # enlarged by the merge step; the characters' frame stays)
+                    from ..postprocess.char_boxes import unpack_chars
+                    if chars is None:     # no detections in the whole group
+                        chars = torch.zeros(tuple(det.scores.shape) + (text.shape[2] + 1, 3), dtype=torch.float32, device=self.device)
+                    extra.update(unpack_chars(chars))
+                    extra["pred_char_frames"] = self._scaled_boxes(det.boxes, sc)
                 res = self.post_processor.process_padded(det.boxes, det.scores, det.counts_dev, text, sc, [shapes[i] for i in idxs],
                                                          extra)
                 for i, r in zip(idxs, res):
@@ -135,6 +150,8 @@ class GlassRunner:
                             # PASTE_MASKS False: the masks' frame follows pred_boxes into the original image's pixels (no word
                             # post-processing on this path, so the two are the same boxes)
                             preds.pred_mask_boxes = preds.pred_boxes.tensor.clone()
+                        if preds.has("pred_char_frames"):        # CHAR_BOXES: the same for the characters' frame
+                            preds.pred_char_frames = preds.pred_boxes.tensor.clone()
                     preds._image_size = tuple(shapes[i])
                     out[i] = preds
         for r in out:
@@ -158,6 +175,9 @@ class GlassRunner:
         (True) or unmerged (False) - `RecognizerRCNNHeadV3.set_pattern(merge_case=...)` for this call only; ValueError if the
         head has no pattern."""
         heads = self.model.roi_heads
+        if _char_boxes_on(self.model):
+            raise NotImplementedError("run_tiled: MODEL.ROI_RECOGNIZER_HEAD.CHAR_BOXES is on; the character rows are not carried "
+                                      "through the cross-tile merge (use run_batch, or switch the key off)")
         if merge_case is not None:
             head = getattr(heads, "recognizer_head", None)
             if getattr(head, "pattern", None) is None:

@@ -68,6 +68,8 @@ class BatchedDetections:
         self.counts_dev, self.counts_host, self.image_sizes = counts_dev, list(counts_host), list(image_sizes)
         self.text = None
         self.text_dist = None         # BEAM_DISTRIBUTIONS: the best hypothesis's full per-step rows, laid out like `text`
+        self.chars = None             # CHAR_BOXES: the packed character rows (postprocess.char_boxes.pack_chars), laid out like `text`
+        self.char_frames = None       # CHAR_BOXES: the boxes the characters lie in, padded [N,K,5] (None: `boxes` themselves)
         self.masks = None             # [sum counts, 1, M, M] mask probabilities (MASK_INFERENCE), or padded [N,K,M,M]
         self.kept_index = None        # [N,K] int32: index into the image's proposal list each detection came from
         self.detected = None          # with override_boxes: the box head's own detections (this object holds the overrides)
@@ -102,6 +104,11 @@ class BatchedDetections:
                 else:
                     s0 = self.roi_start_host[n]
                     r.pred_text_dist = self.text_dist[s0:s0 + c]
+            if self.chars is not None:
+                from ...postprocess.char_boxes import attach_chars
+                s0 = self.roi_start_host[n]
+                frames = self.boxes if self.char_frames is None else self.char_frames
+                attach_chars(r, self.chars[n, :c] if self.chars.dim() == 4 else self.chars[s0:s0 + c], frames[n, :c])
             if self.masks is not None:                        # forward_with_given_boxes, :595-606
                 s0 = self.roi_start_host[n]
                 r.pred_masks = self.masks[s0:s0 + c]
@@ -199,7 +206,7 @@ class MaskRotatedRecognizerHybridHead(InferenceModule):
     def recognizer_branch_batched(self, img_nhwc4: torch.Tensor, feats: Dict[str, torch.Tensor], boxes: torch.Tensor,
                                   roi_image: torch.Tensor, num_images: int, return_intermediates: bool = False, guard=None):
         """boxes [R,5], roi_image int32 [R] -> pred_text_prob [R,26,97] (R > 0; with BEAM_DISTRIBUTIONS the pair
-        (pred_text_prob, pred_text_dist), see recognizer_head_v2.split_text_rows).  `guard`: ops.native.HandoffGuard the caller
+        (pred_text_prob, pred_text_dist), with CHAR_BOXES the triple, see recognizer_head_v2.split_text_rows).  `guard`: ops.native.HandoffGuard the caller
         resolves at its next read-back (None: the recognizer head reads the hand-off status itself, synchronising)."""
         R = boxes.shape[0]
         p2, p3 = feats[self.recognizer_in_features[0]], feats[self.recognizer_in_features[1]]
@@ -318,8 +325,8 @@ class MaskRotatedRecognizerHybridHead(InferenceModule):
         # the one-launch recurrent kernels report a hand-off that gave up into det.handoff.status; the meta-arch reads it with
         # the surviving counts (its next read-back) and, if set, replaces det.text by det.handoff.retry() - the step kernels
         det.handoff = K.HandoffGuard(device)
-        det.text, det.text_dist = split_text_rows(
-            self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts), guard=det.handoff))
+        det.text, det.text_dist, det.chars = split_text_rows(
+            self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts), guard=det.handoff), chars=True)
         if self.mask_inference:
             det.masks = self.mask_branch_batched(feats, boxes, roi_image)
         return det
@@ -334,9 +341,14 @@ class MaskRotatedRecognizerHybridHead(InferenceModule):
             roi_image = K.upload(torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32), torch.tensor(counts)), torch.int32, device)
         # reference: with no boxes the recognizer head returns the instances untouched (recognizer_head_v2.py:151)
         if self.recognizer_on and R > 0:
-            probs, dist = split_text_rows(self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts)))
+            probs, dist, chars = split_text_rows(self.recognizer_branch_batched(img_nhwc4, feats, boxes, roi_image, len(counts)),
+                                                 chars=True)
             for p, r in zip(probs.split(counts, dim=0), results):
                 r.pred_text_prob = p
+            if chars is not None:              # CHAR_BOXES: the characters' frame is the box that was pooled
+                from ...postprocess.char_boxes import attach_chars
+                for ch, r in zip(chars.split(counts, dim=0), results):
+                    attach_chars(r, ch, r.pred_boxes.tensor)
             if dist is not None:
                 for d, r in zip(dist.split(counts, dim=0), results):
                     r.pred_text_dist = d

@@ -182,7 +182,7 @@ class GeneralizedRCNN(InferenceModule):
         if guard is not None:
             again = guard.resolve((yield ReadBack(guard.status))[0][0])
             if again is not None:
-                det.text, det.text_dist = split_text_rows(again)
+                det.text, det.text_dist, det.chars = split_text_rows(again, chars=True)
 
     def _postprocess_batched(self, det, batched_inputs, image_sizes):
         return drive(self._postprocess_batched_g(det, batched_inputs, image_sizes))
@@ -218,7 +218,14 @@ class GeneralizedRCNN(InferenceModule):
                 return None
             return K.detections_finalize(det.boxes, det.scores, None, det.text_dist, det.counts_dev, roi_start, scale_xy, out_hw,
                                          float(self._min_box_dim), self._filter_small)[3]
-        od = finalize_dist()
+
+        def finalize_chars():
+            # CHAR_BOXES: and for the packed character rows
+            if getattr(det, "chars", None) is None:
+                return None
+            return K.detections_finalize(det.boxes, det.scores, None, det.chars, det.counts_dev, roi_start, scale_xy, out_hw,
+                                         float(self._min_box_dim), self._filter_small)[3]
+        od, och = finalize_dist(), finalize_chars()
         if guard is None:
             counts = (yield ReadBack(oc))[0].tolist()
         else:
@@ -228,14 +235,15 @@ class GeneralizedRCNN(InferenceModule):
             counts = host[0].tolist()
             again = guard.resolve(host[1][0])
             if again is not None:
-                det.text, det.text_dist = split_text_rows(again)
+                det.text, det.text_dist, det.chars = split_text_rows(again, chars=True)
                 ob, os_, oo, ot, oc = K.detections_finalize(det.boxes, det.scores, det.orient, det.text, det.counts_dev, roi_start,
                                                             scale_xy, out_hw, float(self._min_box_dim), self._filter_small)
-                od = finalize_dist()
+                od, och = finalize_dist(), finalize_chars()
                 counts = (yield ReadBack(oc))[0].tolist()
         post = BatchedDetections(ob, os_, oo, oc, counts, out_sizes)
         post.text = ot
         post.text_dist = od
+        post.chars = och              # CHAR_BOXES: [N,K,L+1,3]; the characters' frames are the finalized boxes, as pred_mask_boxes
         post.mask_rois = om if not self.paste_masks else None      # PASTE_MASKS False: the finalized mask rows [N, K, M, M]
         self.last_batch = post
         results = post.to_instances()

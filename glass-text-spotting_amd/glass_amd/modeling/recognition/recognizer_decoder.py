@@ -68,16 +68,28 @@ class BeamResult(_BeamFields):
         self.distributions = distributions
         self.words = words
         self.model_scores = model_scores
+        self.attention = None           # beam_decode(attention=True): the replayed attention rows, float32 [B, L, T] / [B, k, L, T]
         return self
 
 
-class ForcedResult(NamedTuple):
-    """`ASTER_V2.score`: device tensors; the n axis is absent where the targets were given as [B, L]"""
+class _ForcedFields(NamedTuple):
     step_logp: torch.Tensor                 # float32 [B, n, L] log-probability of targets[t] at step t; 0 from the length on
     scores: torch.Tensor                    # float32 [B, n] float32 sum of step_logp[:length] in step order
     lengths: torch.Tensor                   # int32 [B, n] steps computed
     probs: Optional[torch.Tensor]           # float32 [B, n, L, C] softmax rows (zero from the length on), or None
     logits: Optional[torch.Tensor]          # float32 [B, n, L, C] raw rows (zero from the length on), or None
+
+
+class ForcedResult(_ForcedFields):
+    """`ASTER_V2.score`: device tensors; the n axis is absent where the targets were given as [B, L].  The tuple keeps its five
+    fields (code that unpacks a result is unaffected); `attention` rides as an attribute, as `BeamResult.model_scores` does:
+    float32 [B, n, L, T], row t = the attention weights over the T encoder positions that formed the context of step t (zero
+    from the length on), with `score(..., attention=True)`; default None."""
+
+    def __new__(cls, step_logp, scores, lengths, probs=None, logits=None, attention=None):
+        self = super().__new__(cls, step_logp, scores, lengths, probs, logits)
+        self.attention = attention
+        return self
 
 
 def build_recognizer_decoderv2(cfg, input_shape):
@@ -219,18 +231,23 @@ class ASTER_V2(InferenceModule):
         t = t.to(torch.int32).contiguous() if t_dev else K.upload(t.contiguous(), torch.int32, device)
         return t, ln, had_n
 
-    def score(self, x: torch.Tensor, targets, lengths=None, eos: int = 0, probs: bool = False, logits: bool = False) -> "ForcedResult":
+    def score(self, x: torch.Tensor, targets, lengths=None, eos: int = 0, probs: bool = False, logits: bool = False,
+              attention: bool = False) -> "ForcedResult":
         """Forced decoding as ONE ABI call (glass_forced_decode): the decoder run with the emitted symbols GIVEN - "how likely
         is this transcription under the model".  x [B,T,D]; targets [B,L] or [B,n,L] (L = max_word_len; n <= 16 sequences per
         item share the item's x rows, which are not inflated): the symbol emitted at each step; lengths [B] / [B,n] or None
         (None: each sequence runs up to and including its first `eos`).  -> ForcedResult on the device: per-step
         log-probabilities of the given symbols, their float32 sum in step order, the lengths, and on request the full softmax
-        rows and raw logits per step; everything from a sequence's length on is zero."""
+        rows and raw logits per step; everything from a sequence's length on is zero.
+        `attention`: the same replay through glass_forced_attention (include/glass_hip_feature_chars.h) - every field bit for
+        bit, and `.attention` [B,n,L,T]: per step the weights over the T encoder positions that formed its context vector
+        (what postprocess.char_boxes turns into character positions)."""
         x = x.contiguous()
         B, T, D = x.shape
         t, ln, had_n = self._targets_to_device(targets, lengths, B, x.device)
         xproj = K.linear(x.view(B * T, D), self.w["xW"], self.w["xB"]).view(B, T, D) if B else x
-        out = K.forced_decode(x, xproj, self.w, t, ln, self.num_classes, self.max_word_len, int(eos), probs=probs, logits=logits)
+        out = K.forced_decode(x, xproj, self.w, t, ln, self.num_classes, self.max_word_len, int(eos), probs=probs, logits=logits,
+                              attention=bool(attention))
         if not had_n:
             out = tuple(o.squeeze(1) if o is not None else None for o in out)
         return ForcedResult(*out)
@@ -263,7 +280,7 @@ class ASTER_V2(InferenceModule):
 
     def beam_decode(self, x: torch.Tensor, beam_width: int, eos: int = 0, path_probs: bool = False,
                     distributions: Optional[str] = None, lexicon=None, segments=None, pattern=None,
-                    weight_scale: float = 1.0, merge_case: bool = False) -> "BeamResult":
+                    weight_scale: float = 1.0, merge_case: bool = False, attention: bool = False) -> "BeamResult":
         """`beam_search` as ONE ABI call (glass_beam_search): every step and the back-tracking on the device, no host
         synchronisation, x / xproj not inflated.  x [B,T,D] -> all `beam_width` hypotheses in final order, on the device;
         `path_probs`: also the best hypothesis as [B, max_word_len, num_classes] rows that the consumers of the greedy
@@ -293,7 +310,11 @@ class ASTER_V2(InferenceModule):
         is the probability of the word, not of one casing.  The hidden state follows the emitted class only.  With a
         case-sensitive pattern every group is one class and the result equals the unmerged search bit for bit.  The replayed
         `distributions` are those of the emitted symbols.  ValueError without `pattern`; with `lexicon=` it names
-        `DecodePattern.from_trie`, the route for a lexicon."""
+        `DecodePattern.from_trie`, the route for a lexicon.
+        `attention`: the replay of hypothesis 0 (with distributions="all": of all k) runs through glass_forced_attention and the
+        result carries `.attention`, float32 [B,L,T] ([B,k,L,T]): per step the weights over the T encoder positions that formed
+        its context vector, zero from the hypothesis's length on (a hypothesis with score -inf: all zero).  With
+        `distributions` it is the SAME replay - one, not two - and the distributions are what they are without it, bit for bit."""
         if merge_case and lexicon is not None:
             raise ValueError("beam_decode: merge_case with lexicon= (pass pattern=DecodePattern.from_trie(lexicon): the merged "
                              "search runs on the pattern tables)")
@@ -323,14 +344,20 @@ class ASTER_V2(InferenceModule):
             out = (res["symbols"], res["scores"], res["lengths"], res["path"])
         else:
             out = K.beam_search(x, xproj, self.w, int(beam_width), self.num_classes, self.max_word_len, int(eos), path_probs=path_probs)
-        dist = None
-        if distributions is not None:
-            n = 1 if distributions == "best" else int(beam_width)
+        dist = att = None
+        if distributions is not None or attention:
+            n = int(beam_width) if distributions == "all" else 1
             sym, sc, ln = out[0][:, :n].contiguous(), out[1][:, :n], out[2][:, :n]
             ln = torch.where(torch.isneginf(sc), torch.zeros_like(ln), ln).contiguous()
-            dist = K.forced_decode(x, xproj, self.w, sym, ln, self.num_classes, self.max_word_len, int(eos), probs=True)[3]
-            dist = dist[:, 0] if distributions == "best" else dist
-        return BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist, words, model_scores)
+            replay = K.forced_decode(x, xproj, self.w, sym, ln, self.num_classes, self.max_word_len, int(eos),
+                                     probs=distributions is not None, attention=bool(attention))
+            if distributions is not None:
+                dist = replay[3] if distributions == "all" else replay[3][:, 0]
+            if attention:
+                att = replay[5] if distributions == "all" else replay[5][:, 0]
+        res = BeamResult(out[0], out[1], out[2], out[3] if path_probs else None, dist, words, model_scores)
+        res.attention = att
+        return res
 
     def forward(self, features: torch.Tensor, labels=None, roi_image: Optional[torch.Tensor] = None,
                 num_images: int = 1, rnn=None, status=None) -> torch.Tensor:

@@ -73,6 +73,10 @@ class RecognizerRCNNHeadV3(InferenceModule):
                                  "(the bonus is a weight on the pattern's transitions)")
             self.set_pattern(self.pattern.weighted(length_bonus=bonus), merge_case=merge)
 
+        # MI355X build only: one forced replay of the emitted symbols (glass_forced_attention) and glass_char_spans add where
+        # inside the pooled box every character lies (postprocess/char_boxes.py); off: no launch and no field is added
+        self.char_boxes = bool(getattr(cfg.MODEL.ROI_RECOGNIZER_HEAD, "CHAR_BOXES", False))
+
     def import_weights(self, sd, device, prefix: str) -> None:
         self.backbone.import_weights(sd, device, prefix + "backbone.")
         self.encoder.import_weights(sd, device, prefix + "encoder.")
@@ -165,7 +169,8 @@ class RecognizerRCNNHeadV3(InferenceModule):
 
     def forward_nhwc(self, x: torch.Tensor, roi_image: torch.Tensor, num_images: int, guard=None):
         """x [R,8,32,256] fused features -> probabilities [R,26,97] (BEAM_WIDTH >= 1: the best hypothesis's path rows; with
-        BEAM_DISTRIBUTIONS the pair (path rows, full distributions [R,26,97] of the best hypothesis) - `split_text_rows`).
+        BEAM_DISTRIBUTIONS the pair (path rows, full distributions [R,26,97] of the best hypothesis) - `split_text_rows`; with
+        CHAR_BOXES the triple (rows, distributions | None, the packed character rows [R,27,3] of postprocess.char_boxes.pack_chars)).
         `guard` (ops.native.HandoffGuard): the one-launch BiLSTM / decoder kernels report a hand-off that gave up into
         `guard.status`, and `guard.retry` re-runs encoder + decoder of THIS call on the step kernels - the caller resolves the
         guard at its next host read-back (GeneralizedRCNN._postprocess_batched_g: the surviving-count read).  Without a guard
@@ -186,11 +191,24 @@ class RecognizerRCNNHeadV3(InferenceModule):
                            "weight_scale": self.weight_scale}
                     if self.merge_case:
                         lex["merge_case"] = True
+                if self.char_boxes:
+                    # ONE replay of the best hypothesis (the search's own symbols and lengths, which the arg-max of its path
+                    # rows up to the first stop spells): its attention rows and, with BEAM_DISTRIBUTIONS, its distributions
+                    r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, attention=True,
+                                                 distributions="best" if self.beam_distributions else None, **lex)
+                    ln = torch.where(torch.isneginf(r.scores[:, 0]), torch.zeros_like(r.lengths[:, 0]), r.lengths[:, 0])
+                    return r.path_probs, r.distributions, self._char_rows(r.attention, r.symbols[:, 0], ln)
                 if self.beam_distributions:
                     r = self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, distributions="best", **lex)
                     return r.path_probs, r.distributions
                 return self.decoder.beam_decode(enc, self.beam_width, self.beam_eos, path_probs=True, **lex).path_probs
-            return self.decoder(enc, roi_image=roi_image, num_images=num_images, rnn=rnn, status=status)
+            rows = self.decoder(enc, roi_image=roi_image, num_images=num_images, rnn=rnn, status=status)
+            if self.char_boxes:
+                # the emitted symbols = the arg-max of the greedy rows, replayed once up to the first stop symbol
+                sym = rows.argmax(dim=-1).to(torch.int32)
+                replay = self.decoder.score(enc, sym, None, eos=self.beam_eos, attention=True)
+                return rows, None, self._char_rows(replay.attention, sym, replay.lengths)
+            return rows
         if self.rnn_override == "steps":
             return run("steps", None)
         out = run(None, guard.status)
@@ -200,10 +218,18 @@ class RecognizerRCNNHeadV3(InferenceModule):
             return out if again is None else again
         return out
 
+    def _char_rows(self, attention: torch.Tensor, symbols: torch.Tensor, lengths: torch.Tensor) -> torch.Tensor:
+        """attention rows [R,L,T] of the replay, its symbols [R,L] and lengths [R] -> the packed character rows [R,L+1,3]"""
+        from ...postprocess.char_boxes import pack_chars
+        return pack_chars(K.char_spans(attention.contiguous(), symbols.contiguous(), lengths.contiguous(), self.beam_eos))
+
     def forward(self, x: torch.Tensor, instances: List[Instances]):
         assert not self.training, "inference only"
         if x.shape[0] == 0:
             return instances
+        if self.char_boxes:
+            raise NotImplementedError("MODEL.ROI_RECOGNIZER_HEAD.CHAR_BOXES: the list-wise forward(x, instances) does not know the "
+                                      "boxes that were pooled; the batched path (GeneralizedRCNN.inference) carries the fields")
         from ..backbone.resnet_fpn import as_nhwc
         counts = [len(i) for i in instances]
         roi_image = K.upload(torch.repeat_interleave(torch.arange(len(counts), dtype=torch.int32), torch.tensor(counts)),
@@ -217,9 +243,12 @@ class RecognizerRCNNHeadV3(InferenceModule):
         return instances
 
 
-def split_text_rows(out):
-    """what `RecognizerRCNNHeadV3.forward_nhwc` returned -> (pred_text_prob rows, pred_text_dist rows | None)"""
-    return out if isinstance(out, tuple) else (out, None)
+def split_text_rows(out, chars: bool = False):
+    """what `RecognizerRCNNHeadV3.forward_nhwc` returned -> (pred_text_prob rows, pred_text_dist rows | None); with `chars` a third
+    member: the packed character rows of CHAR_BOXES (postprocess.char_boxes.pack_chars) | None"""
+    rows = tuple(out) if isinstance(out, tuple) else (out,)
+    rows = rows + (None,) * (3 - len(rows))
+    return rows if chars else rows[:2]
 
 
 def build_recognizer_head(cfg, input_shape):

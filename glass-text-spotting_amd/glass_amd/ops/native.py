@@ -1620,11 +1620,14 @@ def beam_search_wdfa(x: torch.Tensor, xproj: torch.Tensor, weights: dict, beam_w
 
 
 def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: torch.Tensor, lengths: Optional[torch.Tensor],
-                  num_classes: int, max_len: int, eos: int, probs: bool = False, logits: bool = False):
+                  num_classes: int, max_len: int, eos: int, probs: bool = False, logits: bool = False, attention: bool = False):
     """the decoder with the emitted symbols given (glass_forced_decode; reference AttentionRecognitionHead.forward): x, xproj
     [B,T,D] un-inflated, targets int32 [B,n,max_len] and lengths int32 [B,n] (or None: up to and including the first `eos`)
     on x's device -> (step_logp [B,n,max_len], scores [B,n], lengths int32 [B,n], probs [B,n,max_len,C] | None, logits
-    [B,n,max_len,C] | None).  No host synchronisation; limits are checked by the library."""
+    [B,n,max_len,C] | None).  No host synchronisation; limits are checked by the library.
+    `attention`: the same replay through glass_forced_attention (include/glass_hip_feature_chars.h) - every output above bit
+    for bit, and one more trailing element: the attention rows [B,n,max_len,T], row t = the weights over the T encoder
+    positions that formed the context of step t, zero from a sequence's length on."""
     B, T, D, dev = _search_inputs("forced_decode", x, xproj, targets)
     C, L = int(num_classes), int(max_len)
     if targets.dim() != 3 or targets.shape[0] != B or targets.shape[2] != L or targets.device != x.device:
@@ -1641,6 +1644,13 @@ def forced_decode(x: torch.Tensor, xproj: torch.Tensor, weights: dict, targets: 
     w = _decoder_weights(weights)
     nbytes = int(lib().glass_forced_decode_workspace_bytes(B, n, T, D, C, L))
     ws = _workspace(nbytes, dev)
+    if attention:
+        rows_att = torch.empty((B, n, max(L, 0), T), dtype=torch.float32, device=dev)
+        check(lib().glass_forced_attention(_dev(x), _dev(xproj), ctypes.byref(w), B, n, T, D, C, L, int(eos), _dev(targets),
+                                           _opt(lengths), _dev(step_logp), _dev(scores), _dev(out_len), _opt(out_probs),
+                                           _opt(out_logits), _dev(rows_att), _dev(ws), nbytes, stream_handle()),
+              "glass_forced_attention")
+        return step_logp, scores, out_len, out_probs, out_logits, rows_att
     check(lib().glass_forced_decode(_dev(x), _dev(xproj), ctypes.byref(w), B, n, T, D, C, L, int(eos), _dev(targets), _opt(lengths),
                                     _dev(step_logp), _dev(scores), _dev(out_len), _opt(out_probs), _opt(out_logits), _dev(ws),
                                     nbytes, stream_handle()), "glass_forced_decode")
@@ -2370,3 +2380,63 @@ def order_lines(line_boxes: torch.Tensor, line_count: torch.Tensor, line_start: 
     if line_first is not None:
         out["line_first"] = line_first
     return out
+
+
+CHAR_SPANS_MAX_STEPS = 64         # steps of a word and encoder columns of glass_char_spans (include/glass_hip_feature_chars.h):
+CHAR_SPANS_MAX_COLUMNS = 64       # the limits of the decoder searches (max_len <= 64, T <= 64)
+
+
+def char_spans(attention: torch.Tensor, targets: torch.Tensor, lengths: torch.Tensor, eos: int) -> dict:
+    """The attention rows of a forced replay turned into normalised spans along the box's width (glass_char_spans,
+    csrc/char_boxes.hip; include/glass_hip_feature_chars.h has the contract and
+    glass_amd.postprocess.char_boxes.char_spans_host states it in numpy): attention contiguous float32 [R, L, T] (row t = the
+    weights of step t over the T encoder columns), targets contiguous int32 [R, L] (the emitted symbols) and lengths contiguous
+    int32 [R] (steps computed, the stop included) on the same device, L and T at most 64 (ValueError above).
+    -> {"spans" float32 [R,L,2], "centres" [R,L], "spreads" [R,L], "count" int32 [R], "monotone" int32 [R], "valid" int32 [R]}
+    device tensors, zero from a word's count on.  Stream-ordered: one launch, no read-back; R == 0 launches nothing."""
+    if not isinstance(attention, torch.Tensor) or attention.dim() != 3 or not (1 <= int(attention.shape[1]) <= CHAR_SPANS_MAX_STEPS
+                                                                              and 1 <= int(attention.shape[2]) <= CHAR_SPANS_MAX_COLUMNS):
+        raise ValueError(f"char_spans: attention {tuple(getattr(attention, 'shape', ()))}: needs [R, L, T] with 1 <= L <= "
+                         f"{CHAR_SPANS_MAX_STEPS} steps and 1 <= T <= {CHAR_SPANS_MAX_COLUMNS} columns")
+    R, L, T = (int(v) for v in attention.shape)
+    dev = attention.device
+    _f32c(attention, "attention")
+    for name, t, shape in (("targets", targets, (R, L)), ("lengths", lengths, (R,))):
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.device != dev:
+            raise ValueError(f"char_spans: {name} {tuple(getattr(t, 'shape', ()))} on {getattr(t, 'device', None)}: needs "
+                             f"{list(shape)} on {dev}")
+        _i32(t, name)
+    _dev(attention, "attention")
+    spans, centres, spreads, count, monotone, valid = (
+        torch.empty(shape, dtype=dt, device=dev) for shape, dt in (
+            ((R, L, 2), torch.float32), ((R, L), torch.float32), ((R, L), torch.float32), ((R,), torch.int32), ((R,), torch.int32),
+            ((R,), torch.int32)))
+    if R:
+        check(lib().glass_char_spans(attention.data_ptr(), targets.data_ptr(), lengths.data_ptr(), R, L, T, int(eos),
+                                     spans.data_ptr(), centres.data_ptr(), spreads.data_ptr(), count.data_ptr(),
+                                     monotone.data_ptr(), valid.data_ptr(), stream_handle()), "glass_char_spans")
+    return {"spans": spans, "centres": centres, "spreads": spreads, "count": count, "monotone": monotone, "valid": valid}
+
+
+def char_quads(spans: torch.Tensor, count: torch.Tensor, frames: torch.Tensor) -> torch.Tensor:
+    """Spans along a box turned into quads in the image (glass_char_quads, csrc/char_boxes.hip;
+    include/glass_hip_feature_chars.h has the contract): spans contiguous float32 [R, L, 2] and count contiguous int32 [R] as
+    `char_spans` returns them, frames contiguous float32 [R, 5] = (cx, cy, w, h, angle in degrees), the boxes the recogniser
+    pooled, on the same device -> float32 [R, L, 4, 2], the corners in the order of `boxes_to_polygons`, zeros from the count
+    on and for a frame that is not finite or has no extent.  One launch, no read-back; R == 0 launches nothing."""
+    if not isinstance(spans, torch.Tensor) or spans.dim() != 3 or int(spans.shape[2]) != 2 or not 1 <= int(spans.shape[1]) <= CHAR_SPANS_MAX_STEPS:
+        raise ValueError(f"char_quads: spans {tuple(getattr(spans, 'shape', ()))}: needs [R, L, 2] with 1 <= L <= {CHAR_SPANS_MAX_STEPS}")
+    R, L, _ = (int(v) for v in spans.shape)
+    dev = spans.device
+    _f32c(spans, "spans")
+    if not isinstance(count, torch.Tensor) or tuple(count.shape) != (R,) or count.device != dev:
+        raise ValueError(f"char_quads: count {tuple(getattr(count, 'shape', ()))} on {getattr(count, 'device', None)}: needs [{R}] on {dev}")
+    if not isinstance(frames, torch.Tensor) or tuple(frames.shape) != (R, 5) or frames.device != dev:
+        raise ValueError(f"char_quads: frames {tuple(getattr(frames, 'shape', ()))} on {getattr(frames, 'device', None)}: needs [{R}, 5] on {dev}")
+    _i32(count, "count"); _f32c(frames, "frames")
+    _dev(spans, "spans")
+    quads = torch.empty((R, L, 4, 2), dtype=torch.float32, device=dev)
+    if R:
+        check(lib().glass_char_quads(spans.data_ptr(), count.data_ptr(), frames.data_ptr(), R, L, quads.data_ptr(), stream_handle()),
+              "glass_char_quads")
+    return quads

@@ -127,6 +127,13 @@ def detector_postprocess(results: Instances, output_height, output_width, mask_t
         return results
     output_boxes.scale(scale_x, scale_y)
     output_boxes.clip(results.image_size)
+    if results.has("pred_char_frames"):
+        # MODEL.ROI_RECOGNIZER_HEAD.CHAR_BOXES: the characters' frame (a copy of the pooled box, which an inflate step before
+        # this call does not touch) goes into the output's pixels by the same scaling; it is not clipped
+        from ..structures.core import RotatedBoxes
+        frames = RotatedBoxes(results.pred_char_frames.clone())
+        frames.scale(scale_x, scale_y)
+        results.pred_char_frames = frames.tensor
     results = results[output_boxes.nonempty()]
     if results.has("pred_masks") and not paste_masks:
         # MODEL.ROI_MASK_HEAD.PASTE_MASKS False: the RoI masks and a COPY of the boxes the paste would have used (the word
