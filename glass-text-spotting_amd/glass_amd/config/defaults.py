@@ -188,7 +188,14 @@ def add_post_process_config(cfg: CN) -> None:
         # on the device, right behind the line grouping (ops.native.order_lines; the thresholds are those of
         # include/glass_hip_feature_layout.h), and every Instances carries pred_page_rank / pred_block_ids / pred_block_boxes
         # (glass_amd.postprocess.blocks_of and page_text give the blocks and the text on the host)
-        "ORDER_LINES": False, "ORDER_MIN_OVERLAP": 0.1, "BLOCK_MAX_GAP": 0.8, "BLOCK_MIN_HEIGHT_RATIO": 0.7}})
+        "ORDER_LINES": False, "ORDER_MIN_OVERLAP": 0.1, "BLOCK_MAX_GAP": 0.8, "BLOCK_MIN_HEIGHT_RATIO": 0.7,
+        # with GROUP_LINES only (a ValueError without; ORDER_LINES is not needed): True = the lines are also aligned into rows,
+        # cells, tables and columns on the device, behind the line grouping and the page order (ops.native.row_grid; the
+        # thresholds are those of include/glass_hip_feature_grid.h), and every Instances carries pred_row_ids / pred_row_pos /
+        # pred_table_ids / pred_col_ids / pred_row_rank / pred_row_boxes / pred_table_boxes (glass_amd.postprocess.rows_of,
+        # tables_of and rows_text give the rows, the tables and the text on the host)
+        "ALIGN_ROWS": False, "ROW_MIN_OVERLAP": 0.5, "ROW_MIN_HEIGHT_RATIO": 0.5, "COLUMN_MIN_OVERLAP": 0.1,
+        "TABLE_MAX_ROW_GAP": 2.0}})
 
 
 def get_glass_cfg(config_path: str = None, opts=None) -> CN:

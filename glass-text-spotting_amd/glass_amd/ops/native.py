@@ -2382,6 +2382,57 @@ def order_lines(line_boxes: torch.Tensor, line_count: torch.Tensor, line_start: 
     return out
 
 
+ROW_GRID_MAX_K = 1024             # GLASS_ROW_GRID_MAX_K (include/glass_hip_feature_grid.h) = GROUP_LINES_MAX_K
+
+
+def row_grid(line_boxes: torch.Tensor, line_count: torch.Tensor, line_start: Optional[torch.Tensor] = None,
+             row_min_overlap: float = 0.5, row_min_height_ratio: float = 0.5, column_min_overlap: float = 0.1,
+             table_max_row_gap: float = 2.0) -> dict:
+    """The text lines of every image of a batch aligned into rows, cells, tables and columns (glass_row_grid, csrc/row_grid.hip;
+    include/glass_hip_feature_grid.h has the contract and glass_amd.postprocess.row_grid.row_grid_host states it in numpy):
+    line_boxes contiguous float32 [N, K, 5] and line_count contiguous int32 [N] on the same device as `group_lines` returns
+    them, K <= ROW_GRID_MAX_K (ValueError above; a count above K is clamped to K, rows beyond the count are never read),
+    optionally line_start contiguous int32 [N, K + 1].
+    -> {"row_id", "row_pos", "table_id", "col_id", "row_order", "table_rows", "table_cols" [N,K], "row_start" [N,K+1], "row_count",
+    "table_count" [N] (int32), "row_boxes", "table_boxes" float32 [N,K,5]} and, with line_start, "row_first" int32 [N,K]: device
+    tensors, padded as the header says.  A threshold that is not finite or out of range is a ValueError before any launch.
+    Stream-ordered: three launches, no read-back; the workspace is allocated here."""
+    from ..postprocess.row_grid import check_grid_params
+    p = check_grid_params(row_min_overlap, row_min_height_ratio, column_min_overlap, table_max_row_gap)
+    if (not isinstance(line_boxes, torch.Tensor) or line_boxes.dim() != 3 or int(line_boxes.shape[2]) != 5
+            or int(line_boxes.shape[1]) > ROW_GRID_MAX_K):
+        raise ValueError(f"row_grid: line_boxes {tuple(getattr(line_boxes, 'shape', ()))}: needs [N, K, 5] with "
+                         f"K <= {ROW_GRID_MAX_K} lines per image")
+    _f32c(line_boxes, "line_boxes"); _i32(line_count, "line_count")
+    N, K, _ = (int(v) for v in line_boxes.shape)
+    dev = line_boxes.device
+    if tuple(line_count.shape) != (N,) or line_count.device != dev:
+        raise ValueError(f"row_grid: line_count {tuple(line_count.shape)} on {line_count.device}: needs [{N}] on {dev}")
+    if line_start is not None:
+        _i32(line_start, "line_start")
+        if tuple(line_start.shape) != (N, K + 1) or line_start.device != dev:
+            raise ValueError(f"row_grid: line_start {tuple(line_start.shape)} on {line_start.device}: needs [{N}, {K + 1}] on {dev}")
+    _dev(line_boxes, "line_boxes")
+    names = ("row_id", "row_pos", "table_id", "col_id", "row_order", "row_start", "row_boxes", "row_count", "table_boxes",
+             "table_rows", "table_cols", "table_count")            # the order of the entry point's output pointers
+    shapes = {"row_start": (N, K + 1), "row_boxes": (N, K, 5), "table_boxes": (N, K, 5), "row_count": (N,), "table_count": (N,)}
+    out = {name: torch.empty(shapes.get(name, (N, K)), dtype=torch.float32 if name.endswith("_boxes") else torch.int32, device=dev)
+           for name in names}
+    row_first = torch.empty((N, K), dtype=torch.int32, device=dev) if line_start is not None else None
+    if N:
+        ws_bytes = int(lib().glass_row_grid_workspace_bytes(N, K))
+        ws = _workspace(ws_bytes, dev)                   # needs no initialisation
+        par = (ctypes.c_double * 4)(p["row_min_overlap"], p["row_min_height_ratio"], p["column_min_overlap"], p["table_max_row_gap"])
+        check(lib().glass_row_grid(line_boxes.data_ptr(), _dev(line_count, "line_count"),
+                                   _dev(line_start, "line_start") if line_start is not None else None, N, K, par,
+                                   *(out[name].data_ptr() for name in names),
+                                   row_first.data_ptr() if row_first is not None else None, _dev(ws), ws_bytes,
+                                   stream_handle()), "glass_row_grid")
+    if row_first is not None:
+        out["row_first"] = row_first
+    return out
+
+
 CHAR_SPANS_MAX_STEPS = 64         # steps of a word and encoder columns of glass_char_spans (include/glass_hip_feature_chars.h):
 CHAR_SPANS_MAX_COLUMNS = 64       # the limits of the decoder searches (max_len <= 64, T <= 64)
 

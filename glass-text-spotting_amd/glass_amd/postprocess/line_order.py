@@ -10,8 +10,9 @@ full-width line separates what is above it from what is below).  The order is a 
 emits the ready line with the smallest key (mv, mu, index); on a cycle it emits the smallest un-emitted line and counts it
 in `forced`.  Blocks are the maximal runs of the order whose neighbours overlap, descend, lie close and have like heights.
 
-Known limits: two pieces of one row that the line grouping left apart (a table) read column by column; L-shaped regions and
-text at angles far from the page's follow the rules, not a human.
+Known limits: two pieces of one row that the line grouping left apart (a table) read column by column (row_grid.py,
+POST_PROCESSING.ALIGN_ROWS, keeps them together); L-shaped regions and text at angles far from the page's follow the rules,
+not a human.
 """
 from __future__ import annotations
 

@@ -112,6 +112,14 @@ class PostProcessorRotatedBoxes:
                 raise ValueError("POST_PROCESSING.ORDER_LINES orders the lines that POST_PROCESSING.GROUP_LINES makes: switch it on too")
             from .line_order import check_order_params
             self.order_params = check_order_params(pp.ORDER_MIN_OVERLAP, pp.BLOCK_MAX_GAP, pp.BLOCK_MIN_HEIGHT_RATIO)
+        # rows, cells, tables and columns on top of the lines (off by default: no launch, no field)
+        self.grid_params = None
+        if pp.get("ALIGN_ROWS", False):
+            if self.line_params is None:
+                raise ValueError("POST_PROCESSING.ALIGN_ROWS aligns the lines that POST_PROCESSING.GROUP_LINES makes: switch it on too")
+            from .row_grid import check_grid_params
+            self.grid_params = check_grid_params(pp.ROW_MIN_OVERLAP, pp.ROW_MIN_HEIGHT_RATIO, pp.COLUMN_MIN_OVERLAP,
+                                                 pp.TABLE_MAX_ROW_GAP)
 
     # ------------------------------------------------------------------ device path (default)
     text_threshold = None          # set by PostProcessorAcademic
@@ -152,6 +160,17 @@ class PostProcessorRotatedBoxes:
             prank = page["line_first"].long().gather(1, row) + lpos
             bid = page["block_id"].long().gather(1, row)
             bbox = page["block_boxes"].gather(1, bid.clamp(min=0)[:, :, None].expand(-1, -1, 5))
+        grid = None
+        if lines is not None and self.grid_params is not None:         # behind the lines (and the page order), before the read-back
+            grid = K.row_grid(lines["line_boxes"], lines["line_count"], lines["line_start"], **self.grid_params)
+            out.update(grid)
+            # per word: its row-major rank is the words ahead of its line plus its position; it carries its line's row, cell,
+            # table and column and the boxes of the row and the table (zeros where the line has no table)
+            grank = grid["row_first"].long().gather(1, row) + lpos
+            grid_ids = [grid[k].long().gather(1, row) for k in ("row_id", "row_pos", "table_id", "col_id")]
+            grbox = grid["row_boxes"].gather(1, grid_ids[0].clamp(min=0)[:, :, None].expand(-1, -1, 5))
+            gtbox = grid["table_boxes"].gather(1, grid_ids[2].clamp(min=0)[:, :, None].expand(-1, -1, 5))
+            gtbox = torch.where((grid_ids[2] >= 0)[:, :, None], gtbox, torch.zeros_like(gtbox))
         from ..utils.pipeline import ReadBack, StepOutput
         if use_text:          # one read-back (generator form: utils/pipeline.py) of counts, characters and lengths
             h_count, h_char, h_len = yield ReadBack(out["count"], out["char"], out["text_len"])
@@ -178,6 +197,9 @@ class PostProcessorRotatedBoxes:
                 r.pred_reading_rank, r.pred_line_boxes = lrank[n, :c], lbox[n, :c]
             if page is not None:
                 r.pred_page_rank, r.pred_block_ids, r.pred_block_boxes = prank[n, :c], bid[n, :c], bbox[n, :c]
+            if grid is not None:
+                r.pred_row_ids, r.pred_row_pos, r.pred_table_ids, r.pred_col_ids = (g[n, :c] for g in grid_ids)
+                r.pred_row_rank, r.pred_row_boxes, r.pred_table_boxes = grank[n, :c], grbox[n, :c], gtbox[n, :c]
             if use_text:
                 from .post_processor_academic import strip_special
                 r.pred_text_scores = out["text_score"][n, :c]
