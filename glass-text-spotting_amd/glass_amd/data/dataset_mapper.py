@@ -6,7 +6,11 @@ Mirrors reference glass/data/dataset_mapper.py:17-168 for inference: read the im
 [d2-recall]) and hand the model a uint8 CHW "image" (:110).  The resize is PIL's bilinear on the uint8 image, done on the
 device byte for byte (ops.native.pil_resize_u8).  With `fused=True` the mapper only uploads the image and names the target
 size; the model's preprocess_image then resizes, normalises and pads in one launch pair (ops.native.pil_resize_into_batch).
-Ground-truth annotations are dropped, not transformed; training (crop, rotation, annotation transforms) is out of scope.
+Ground-truth annotations are dropped, not transformed; training (crop, random rotation, annotation transforms) is out of
+scope.  `rotate` (degrees, counter-clockwise) is the rotated-image evaluation: the decoded uint8 image is rotated before the
+resize as `PIL.Image.rotate(angle, BILINEAR, expand=True, fillcolor=rotate_fill)` rotates it, on the device byte for byte
+(ops.native.rotate_u8), and the output carries the `RotationTransform` that moves ground truth and boxes with it
+(evaluation/rotated.py).
 """
 from __future__ import annotations
 
@@ -16,7 +20,7 @@ import numpy as np
 import torch
 
 from ..ops import native as K
-from .transforms import ResizeShortestEdge, pil_resize_u8_host
+from .transforms import ResizeShortestEdge, RotationTransform, check_fill, pil_resize_u8_host, rotate_u8_host
 
 
 def rgb2grey_three_channels(image: np.ndarray) -> np.ndarray:
@@ -44,9 +48,12 @@ class DatasetMapper:
     decoded "image": uint8 HWC in cfg.INPUT.FORMAT channel order (for GREY: RGB, converted here as GlassRunner converts its
     input).  "annotations" are dropped; "file_name" and every other key are kept, "height" / "width" are the original
     image's.  fused=False: "image" = the resized uint8 CHW tensor, the reference mapper's output.  fused=True: the raw
-    form {"image_u8": uint8 [H,W,3] on the device, "resize": (Ho, Wo)} that GeneralizedRCNN.preprocess_image resizes."""
+    form {"image_u8": uint8 [H,W,3] on the device, "resize": (Ho, Wo)} that GeneralizedRCNN.preprocess_image resizes.
+    rotate != 0 (degrees; the attribute may be set between calls): the image is rotated after the GREY conversion and the size
+    check and before the resize, "height" / "width" are the ROTATED image's (the model and the writer see the rotated file),
+    and "rotation" is the RotationTransform.  rotate == 0: the dict is what it is without the feature and nothing is launched."""
 
-    def __init__(self, cfg, is_train: bool = False, device=None, fused: bool = True):
+    def __init__(self, cfg, is_train: bool = False, device=None, fused: bool = True, rotate: float = 0.0, rotate_fill=(0, 0, 0)):
         if is_train:
             raise NotImplementedError("glass_amd builds the inference hot path only; training is out of scope")
         self.img_format = cfg.INPUT.FORMAT
@@ -55,6 +62,15 @@ class DatasetMapper:
         self.device = torch.device(device if device is not None else cfg.MODEL.DEVICE)
         self.fused = bool(fused)
         self.is_train = False
+        self.rotate = self.check_rotate(rotate)
+        self.rotate_fill = check_fill(rotate_fill)
+
+    @staticmethod
+    def check_rotate(angle) -> float:
+        angle = float(angle)
+        if not np.isfinite(angle):
+            raise ValueError(f"rotate {angle}: needs a finite angle in degrees")
+        return angle
 
     def _host_image(self, dataset_dict: Dict) -> np.ndarray:
         if dataset_dict.get("image") is not None:
@@ -77,9 +93,18 @@ class DatasetMapper:
             if key in dataset_dict and int(dataset_dict[key]) != (h, w)[key == "width"]:
                 raise ValueError(f"{dataset_dict.get('file_name')}: {key} {dataset_dict[key]} does not match the image {h}x{w}")
         out = {k: v for k, v in dataset_dict.items() if k not in ("annotations", "image")}
+        rotation = None
+        if self.check_rotate(self.rotate) != 0.0:
+            rotation = RotationTransform(h, w, self.rotate)
+            h, w = rotation.out_hw
+            out["rotation"] = rotation
         out["height"], out["width"] = h, w
         out_hw = self.resize.get_output_shape(h, w)
+        if rotation is not None and self.device.type != "cuda":
+            image = rotate_u8_host(image, rotation, self.rotate_fill)
         u8 = torch.from_numpy(image).to(self.device)
+        if rotation is not None and self.device.type == "cuda":
+            u8 = K.rotate_u8(u8, rotation, self.rotate_fill)
         if self.fused:
             out["image_u8"], out["resize"] = u8, out_hw
         elif self.device.type == "cuda":

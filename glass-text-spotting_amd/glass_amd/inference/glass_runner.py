@@ -68,19 +68,26 @@ class GlassRunner:
         scale_ratio = self.get_inference_scale_ratio(original_image.shape)
         return self._image_at_scale(original_image, scale_ratio), scale_ratio
 
-    def _image_at_scale(self, original_image: np.ndarray, scale_ratio):
-        """the device image `_image_to_tensor` makes, at a ratio of the caller's choice"""
+    def _grey(self, original_image: np.ndarray) -> np.ndarray:
         if self.input_format == "GREY":
             # reference glass/utils/common_utils.py:29-43 (rgb2grey, three_channels=True), on the host uint8 image as
             # the reference does: Y'709 weights on channels 0,1,2, truncated to uint8, replicated three times
             g = np.uint8(0.2125 * original_image[:, :, 0] + 0.7154 * original_image[:, :, 1] + 0.0721 * original_image[:, :, 2])
             original_image = np.repeat(g[:, :, None], 3, axis=2)
-        height, width = original_image.shape[:2]
+        return original_image
+
+    def _image_at_scale(self, original_image, scale_ratio):
+        """the device image `_image_to_tensor` makes, at a ratio of the caller's choice.  A uint8 HWC tensor already on the
+        device (run_rotated's rotated image: converted to grey before it was uploaded) skips the conversion and the upload."""
+        if isinstance(original_image, torch.Tensor):
+            u8 = original_image
+        else:
+            u8 = torch.from_numpy(np.ascontiguousarray(self._grey(original_image))).to(self.device)
+        height, width = (int(v) for v in u8.shape[:2])
         if scale_ratio != 1:
             nh, nw = int(np.round(scale_ratio * height)), int(np.round(scale_ratio * width))
         else:
             nh, nw = height, width
-        u8 = torch.from_numpy(np.ascontiguousarray(original_image)).to(self.device)
         return K.image_u8hwc_to_chw(u8, (nh, nw), flip_channels=(self.input_format == "RGB"))
 
     @staticmethod
@@ -99,7 +106,7 @@ class GlassRunner:
             t, r = self._image_to_tensor(im)
             inputs.append({"image": t, "height": t.shape[1], "width": t.shape[2]})
             ratios.append(r)
-            shapes.append(im.shape[:2])
+            shapes.append(tuple(int(v) for v in im.shape[:2]))
         d = self.model.backbone.size_divisibility
         groups = {}
         for i, inp in enumerate(inputs):
@@ -302,6 +309,49 @@ class GlassRunner:
                 res.pred_mask_boxes = res.pred_boxes.tensor.clone()
         self.logger.info(f"Tiled inference: {len(plan.tiles)} tiles{' + the full view' if with_full else ''}, {n_out} merged "
                          f"detections, {len(res)} word instances")
+        return res
+
+    def run_rotated(self, image: np.ndarray, angle: float, fill=(0, 0, 0)) -> Instances:
+        """The robustness probe and the deskewing primitive: the words of `image` as the model reads them when the image is
+        turned by `angle` degrees (counter-clockwise) first, returned in the ORIGINAL image's frame.  The image is converted to
+        grey on the host where the format asks for it, uploaded once and rotated on the device as
+        `PIL.Image.rotate(angle, BILINEAR, expand=True, fillcolor=fill)` rotates it (ops.native.rotate_u8, byte for byte); the
+        front end, the model and the post-processor then run on the rotated image exactly as `run_batch` runs them, in the
+        rotated frame, and `pred_boxes` - and, where present, `pred_mask_boxes` and `pred_char_frames` - come back through the
+        inverse map (ops.native.rotate_boxes: the centre through the matrix, the angle minus `angle`, wrapped into
+        [-180, 180)); the corners in `pred_polygons` go through the same matrix as points.  The image size of the result is the original's.  At angle % 360 == 0 this is `run_batch([image])[0]`.
+        Pasted masks (rasters in the rotated frame) and the line, block, row and table fields are not mapped:
+        NotImplementedError with MODEL.ROI_MASK_HEAD.MASK_INFERENCE and PASTE_MASKS True, and with
+        POST_PROCESSING.GROUP_LINES."""
+        from ..data.transforms import RotationTransform, check_fill
+        angle = float(angle)
+        if not np.isfinite(angle):
+            raise ValueError(f"run_rotated: angle {angle}")
+        fill = check_fill(fill)
+        if angle % 360.0 == 0.0:
+            return self.run_batch([image])[0]
+        if bool(getattr(self.model.roi_heads, "mask_inference", False)) and getattr(self.model, "paste_masks", True):
+            raise NotImplementedError("run_rotated: MODEL.ROI_MASK_HEAD.MASK_INFERENCE is on and the masks are pasted in the rotated "
+                                      "image's frame; set MODEL.ROI_MASK_HEAD.PASTE_MASKS False to carry the RoI masks "
+                                      "(pred_mask_rois / pred_mask_boxes) instead")
+        if bool(self.cfg.POST_PROCESSING.GROUP_LINES):
+            raise NotImplementedError("run_rotated: POST_PROCESSING.GROUP_LINES is on; the line, block, row and table boxes (and "
+                                      "their padding rows) are not mapped back from the rotated frame")
+        height, width = image.shape[:2]
+        rotation = RotationTransform(height, width, angle)
+        u8 = torch.from_numpy(np.ascontiguousarray(self._grey(image))).to(self.device)
+        res = self.run_batch([K.rotate_u8(u8, rotation, fill)])[0]
+        res.pred_boxes = RotatedBoxes(K.rotate_boxes(res.pred_boxes.tensor.contiguous(), rotation, inverse=True))
+        for name in ("pred_mask_boxes", "pred_char_frames"):
+            if res.has(name):
+                res.set(name, K.rotate_boxes(res.get(name).contiguous(), rotation, inverse=True))
+        if res.has("pred_polygons"):
+            # the words' corners [R, 4, 2] are points: through the matrix itself, in float64, rounded once (a few small
+            # launches; RotationTransform.inverse_coords is the same statement on the host)
+            p, m = res.pred_polygons.double(), rotation.matrix
+            x, y = p[..., 0], p[..., 1]
+            res.pred_polygons = torch.stack([m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]], -1).float()
+        res._image_size = (int(height), int(width))
         return res
 
     def __call__(self, original_image: np.ndarray) -> Instances:

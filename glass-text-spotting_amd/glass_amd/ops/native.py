@@ -2491,3 +2491,47 @@ def char_quads(spans: torch.Tensor, count: torch.Tensor, frames: torch.Tensor) -
         check(lib().glass_char_quads(spans.data_ptr(), count.data_ptr(), frames.data_ptr(), R, L, quads.data_ptr(), stream_handle()),
               "glass_char_quads")
     return quads
+
+
+def rotate_u8(img: torch.Tensor, transform_or_angle, fill=(0, 0, 0)) -> torch.Tensor:
+    """`PIL.Image.rotate(angle, BILINEAR, expand=True, fillcolor=fill)` of a device uint8 HWC image, byte for byte
+    (glass_rotate_u8, csrc/image_rotate.hip; include/glass_hip_feature_rotate.h has the contract and
+    data.transforms.rotate_u8_host states it in numpy): img contiguous uint8 [H, W, 3]; `transform_or_angle` a
+    data.transforms.RotationTransform of that size, or an angle in degrees (counter-clockwise) from which one is made
+    -> uint8 [Ho, Wo, 3] on the same device, (Ho, Wo) = the transform's out_hw.  A fill outside 0..255, a non-finite angle or a
+    transform of another size is a ValueError.  Stream-ordered: one launch, no host synchronisation."""
+    from ..data.transforms import RotationTransform, check_fill
+    if not isinstance(img, torch.Tensor) or img.dtype != torch.uint8 or not img.is_contiguous() or img.dim() != 3 or img.shape[2] != 3:
+        raise GlassLibraryError("image must be contiguous uint8 HWC with 3 channels")
+    _dev(img, "image")
+    H, W = int(img.shape[0]), int(img.shape[1])
+    t = transform_or_angle if isinstance(transform_or_angle, RotationTransform) else RotationTransform(H, W, transform_or_angle)
+    if (t.h, t.w) != (H, W):
+        raise ValueError(f"rotate_u8: {t!r} on a {H}x{W} image")
+    fill = check_fill(fill)
+    Ho, Wo = t.out_hw
+    out = torch.empty((Ho, Wo, 3), dtype=torch.uint8, device=img.device)
+    check(lib().glass_rotate_u8(img.data_ptr(), H, W, out.data_ptr(), Ho, Wo, (ctypes.c_double * 6)(*t.matrix), t.kind, *fill,
+                                stream_handle()), "glass_rotate_u8")
+    return out
+
+
+def rotate_boxes(boxes: torch.Tensor, transform, inverse: bool = False) -> torch.Tensor:
+    """Rotated boxes (cx, cy, w, h, angle) moved with the image (glass_rotate_boxes, csrc/image_rotate.hip;
+    data.transforms.RotationTransform.apply_rotated_boxes / inverse_rotated_boxes state it in numpy): boxes contiguous
+    float32 [..., 5] on the device -> a new tensor of the same shape; `inverse` brings boxes of the rotated image back to the
+    original's frame.  Rows with a non-finite value are copied bit for bit.  One launch, no read-back; no box, no launch."""
+    from ..data.transforms import RotationTransform
+    if not isinstance(transform, RotationTransform):
+        raise ValueError(f"rotate_boxes: needs a RotationTransform, got {type(transform).__name__}")
+    if not isinstance(boxes, torch.Tensor) or boxes.dim() < 1 or int(boxes.shape[-1]) != 5:
+        raise ValueError(f"rotate_boxes: boxes {tuple(getattr(boxes, 'shape', ()))}: needs [..., 5]")
+    _f32c(boxes, "boxes")
+    _dev(boxes, "boxes")
+    n = boxes.numel() // 5
+    out = torch.empty_like(boxes)
+    if n:
+        m, theta = (transform.matrix, -transform.angle) if inverse else (transform.inverse_matrix, transform.angle)
+        check(lib().glass_rotate_boxes(boxes.data_ptr(), n, (ctypes.c_double * 6)(*m), float(theta), out.data_ptr(),
+                                       stream_handle()), "glass_rotate_boxes")
+    return out
