@@ -119,8 +119,10 @@ __device__ __forceinline__ void rows_topk(int k, int C, int u, int lane, int wav
       if (vi != 0x7fffffff && (gi == 0x7fffffff || vb > gb || (vb == gb && vi < gi))) { gb = vb; gi = vi; }
     }
     // k <= C: a candidate is always left and gi is a real index - unless the logits hold NaN (outside the contract):
-    // the tables must still hold valid slots and classes, they index memory in the later steps and in the finalisation
-    if (gi == 0x7fffffff) gi = j;
+    // the tables must still hold valid slots and classes, they index memory in the later steps and in the finalisation, and
+    // a score that is a number: where all of wave 0's 64 lanes hold NaN so does its maximum gb, and beam_rank, which gives
+    // every NaN rank 0, would leave result slots of the back-tracking unassigned
+    if (gi == 0x7fffffff) { gi = j; gb = -INFINITY; }
     const int beam = gi / C, cls = gi - beam * C;
     if (u == cls) taken |= 1u << beam;
     if (u == 0) emit(j, gb, beam, cls);
@@ -158,8 +160,10 @@ __device__ __forceinline__ void rows_topk_by(int k, int C, int u, int lane, int 
       if (vi != 0x7fffffff && (gi == 0x7fffffff || vb > gb || (vb == gb && vi < gi))) { gb = vb; gi = vi; }
     }
     // k <= C: a candidate is always left and gi is a real index - unless the logits hold NaN (outside the contract):
-    // the tables must still hold valid slots and classes, they index memory in the later steps and in the finalisation
-    if (gi == 0x7fffffff) gi = j;
+    // the tables must still hold valid slots and classes, they index memory in the later steps and in the finalisation, and
+    // a score that is a number: where all of wave 0's 64 lanes hold NaN so does its maximum gb, and beam_rank, which gives
+    // every NaN rank 0, would leave result slots of the back-tracking unassigned
+    if (gi == 0x7fffffff) { gi = j; gb = -INFINITY; }
     const int beam = gi / C, cls = gi - beam * C;
     if (u == cls) taken |= 1u << beam;
     if (u == 0) emit(j, gb, beam, cls);

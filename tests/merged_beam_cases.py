@@ -98,7 +98,7 @@ def replay_with(step, state, B, k, C, L, eos, keys, item_roots, item_weights=Non
                     a = beam["acc"] + w.symbol(beam["prefix"], key)
                     cands.append(dict(fused=m + scale * a, model=m, acc=a, slot=r, cls=rep, key=key,
                                       rep_gap=rest[0] - rest[1] if len(rest) > 1 else math.inf))
-            cands.sort(key=lambda c: -c["fused"])
+            cands.sort(key=lambda c: (-c["fused"], c["slot"] * C + c["cls"]))     # ties: the flat index of the representative
             chosen = cands[:k]
             if len(cands) > k:
                 margin[b] = min(float(margin[b]), chosen[-1]["fused"] - cands[k]["fused"])
