@@ -1,6 +1,7 @@
 """`GlassRunner`: the single-image predictor the reference ships, on the HIP pipeline.
 
 `run_tiled` is the large-image form: overlapping tiles at full resolution as one batch, merged on the device.
+`run_views` is test-time augmentation: rotated and rescaled views of one image, fused on the device.
 
 Mirrors reference glass/inference/glass_runner.py:20-153: cfg set-up (:31-39), model build and
 checkpoint load (:52-60), channel handling (:83-87), on-device bilinear resize policy
@@ -352,6 +353,144 @@ class GlassRunner:
             x, y = p[..., 0], p[..., 1]
             res.pred_polygons = torch.stack([m[0] * x + m[1] * y + m[2], m[3] * x + m[4] * y + m[5]], -1).float()
         res._image_size = (int(height), int(width))
+        return res
+
+    def run_views(self, image: np.ndarray, angles=(0.0, 90.0, 180.0, 270.0), scales=(1.0,), fill=(0, 0, 0), rank: str = "product",
+                  min_votes: int = 1, nms_thresh: Optional[float] = None, batch_size: int = 8) -> Instances:
+        """Test-time augmentation: the image at every rotation of `angles` (degrees counter-clockwise, rotated on the device as
+        run_rotated rotates it) times every scale of `scales` (1.0: what `__call__` would feed for the rotated image), fused
+        into ONE detection set in the original image's frame (view_fusion.plan_views, ops.native.fuse_views =
+        glass_fuse_views).  Of the copies of a word that several views hold (rotated IoU >= `nms_thresh`, default
+        MODEL.ROI_HEADS.NMS_THRESH_TEST, between boxes of different views) the one with the best key stays: `rank` "product"
+        = detection score times word score, "word" = the word score alone, "detection" = the detection score alone - the
+        upside-down copy of a word is detected as well as the upright one but read badly.  A detection whose centre lies
+        outside the image (the fill corners of a rotated canvas) is dropped, and so is one that fewer than `min_votes` views
+        found.  The fused set - at most 1024 detections - takes the ordinary way through the word post-processor, with the
+        boxes in the original image's pixels.  Per word: `pred_view_votes` (how many views found it), `pred_view` (the view of
+        the copy that was kept: index into the angle-major, scale-minor list) and `pred_view_mask` (bit v: view v), all int64;
+        `orientations` are carried as that view emitted them, in its frame."""
+        from ..data.transforms import check_fill
+        from .view_fusion import plan_views
+        heads = self.model.roi_heads
+        if _char_boxes_on(self.model):
+            raise NotImplementedError("run_views: MODEL.ROI_RECOGNIZER_HEAD.CHAR_BOXES is on; the character rows are not carried "
+                                      "through the fusion of views (use run_rotated, or switch the key off)")
+        with_masks = bool(getattr(heads, "mask_inference", False))
+        if with_masks and getattr(self.model, "paste_masks", True):
+            raise NotImplementedError("run_views: MODEL.ROI_MASK_HEAD.MASK_INFERENCE is on and the masks are pasted per view frame, "
+                                      "which cannot be fused; set MODEL.ROI_MASK_HEAD.PASTE_MASKS False to carry the RoI masks "
+                                      "(pred_mask_rois / pred_mask_boxes) instead")
+        if getattr(getattr(heads, "recognizer_head", None), "image_segments", None) is not None:
+            raise NotImplementedError("run_views: the recogniser head carries per-image lexicon segments (image_segments); the "
+                                      "views of one image are not images of that list - set the lexicon with one segment")
+        if getattr(self.model, "inflate_ratio", None) or getattr(self.model, "drop_overlapping_boxes", None):
+            raise NotImplementedError("run_views needs the model's padded device batch; POST_PROCESSING.INFLATE_RATIO / "
+                                      "POST_PROCESSING.DROP_OVERLAPPING take the list-wise path, which has none")
+        if rank not in ("detection", "product", "word"):
+            raise ValueError(f"run_views: rank={rank!r} (one of detection, product, word)")
+        fill = check_fill(fill)
+        height, width = (int(v) for v in image.shape[:2])
+        views = plan_views(height, width, angles, scales, self.get_inference_scale_ratio)
+        V, Kdet, min_votes = len(views), int(self.cfg.TEST.DETECTIONS_PER_IMAGE), int(min_votes)
+        if V * Kdet > K.FUSE_VIEWS_MAX_SLOTS:
+            raise ValueError(f"run_views: {V} views of {Kdet} detections each exceed the {K.FUSE_VIEWS_MAX_SLOTS} slots of one "
+                             f"fusion (at most {K.FUSE_VIEWS_MAX_SLOTS // Kdet} views at TEST.DETECTIONS_PER_IMAGE {Kdet})")
+        if not 1 <= min_votes <= V:
+            raise ValueError(f"run_views: min_votes={min_votes} with {V} views (1..{V})")
+        dev = self.device
+        # ---- the views: one upload, a rotation per angle, the front end per view
+        u8 = torch.from_numpy(np.ascontiguousarray(self._grey(image))).to(dev)
+        rotated, inputs = {}, []
+        for view in views:
+            key = id(view.rotation)
+            if key not in rotated:
+                rotated[key] = u8 if view.rotation.kind == 0 else K.rotate_u8(u8, view.rotation, fill)
+            t = self._image_at_scale(rotated[key], view.rho)
+            inputs.append({"image": t, "height": t.shape[1], "width": t.shape[2]})
+        # ---- the model: views grouped by padded shape (run_batch), calls of at most batch_size, joined along the view axis
+        d = self.model.backbone.size_divisibility
+        groups = {}
+        for i, inp in enumerate(inputs):
+            groups.setdefault(((inp["height"] + d - 1) // d * d, (inp["width"] + d - 1) // d * d), []).append(i)
+        step = max(int(batch_size), 1)
+        calls = [idxs[i:i + step] for idxs in groups.values() for i in range(0, len(idxs), step)]
+        dets = []
+        for call in calls:
+            det = getattr(self.model([inputs[i] for i in call]), "batch", None)
+            if det is None:
+                raise RuntimeError("run_views needs the model's padded device batch")
+            if tuple(det.scores.shape) != (len(call), Kdet):
+                raise RuntimeError(f"run_views: a batch of scores {tuple(det.scores.shape)}, expected {(len(call), Kdet)}")
+            dets.append(det)
+        perm = [i for call in calls for i in call]                 # row r of the joined batches is view perm[r]
+        back = None
+        if perm != list(range(V)):
+            back = K.upload(np.argsort(np.asarray(perm)), torch.int64, dev)
+
+        def joined(name, tail):
+            parts = [getattr(dt, name, None) for dt in dets]
+            if all(p is None for p in parts):
+                return None
+            t = torch.cat([p if p is not None else torch.zeros((dt.scores.shape[0], Kdet) + tail, dtype=torch.float32, device=dev)
+                           for p, dt in zip(parts, dets)], 0)
+            return t if back is None else t.index_select(0, back)
+        T = self.cfg.MODEL.ROI_RECOGNIZER_HEAD.MAX_WORD_LENGTH + 1
+        C = len(self.cfg.MODEL.ROI_RECOGNIZER_HEAD.CHARACTER_SET) + 2
+        boxes, scores = joined("boxes", (5,)), joined("scores", ())
+        orient, text, text_dist = joined("orient", (2,)), joined("text", (T, C)), joined("text_dist", (T, C))
+        counts = torch.cat([dt.counts_dev for dt in dets], 0)
+        counts = (counts if back is None else counts.index_select(0, back)).contiguous()
+        if text is None and sum(sum(dt.counts_host) for dt in dets) > 0:
+            raise RuntimeError("recognizer output missing")
+        rois = None
+        if with_masks:       # PASTE_MASKS False: the views' mask rows [n, K, M, M] (a call without a detection has none)
+            have = [dt.mask_rois for dt in dets if getattr(dt, "mask_rois", None) is not None]
+            rois = joined("mask_rois", tuple(have[0].shape[2:])) if have else None
+        # ---- the keys' text rows, the fusion, and the survivors' rows gathered by their source slot
+        arg = mx = None
+        if rank != "detection":
+            if text is not None:
+                arg, mx = K.text_argmax(text.contiguous(), counts)
+            else:            # no detection in any view
+                arg = torch.zeros((V, Kdet, T), dtype=torch.int32, device=dev)
+                mx = torch.zeros((V, Kdet, T), dtype=torch.float32, device=dev)
+        thr = float(self.cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST if nms_thresh is None else nms_thresh)
+        stop = self.post_processor.text_encoder.character.index("[s]")
+        m = K.fuse_views(boxes.contiguous(), scores.contiguous(), counts, K.upload([list(v.affine) for v in views], torch.float64, dev),
+                         K.upload([0.0, 0.0, float(width), float(height)], torch.float32, dev), thr, arg, mx, stop, rank,
+                         min_votes, K.FUSE_VIEWS_MAX_OUT)
+        src = m["src"].long()
+        gather = lambda t: None if t is None else t.reshape((V * Kdet,) + tuple(t.shape[2:])).index_select(0, src).unsqueeze(0)
+        orient, text, text_dist, rois = gather(orient), gather(text), gather(text_dist), gather(rois)
+        votes, view_of, mask = m["votes"].long().unsqueeze(0), (src // Kdet).unsqueeze(0), m["views"].unsqueeze(0)
+        n_out, truncated, n_kept = m["count"].tolist()             # the one read of out_count
+        if truncated:
+            self.logger.warning(f"run_views: more than {K.FUSE_VIEWS_MAX_OUT} fused detections; the lowest-ranked are cut off")
+        if self.post_process_flag:
+            if text is None:          # no detections in any view
+                text = torch.zeros((1, K.FUSE_VIEWS_MAX_OUT, T, C), dtype=torch.float32, device=dev)
+            one = torch.ones((1, 2), dtype=torch.float32, device=dev)
+            extra = {"orientations": orient, "pred_text_dist": text_dist, "pred_view_votes": votes, "pred_view": view_of,
+                     "pred_view_mask": mask}
+            if rois is not None:      # the masks' frame: the fused boxes, before word post-processing, in the original's pixels
+                extra["pred_mask_rois"] = rois
+                extra["pred_mask_boxes"] = m["boxes"].unsqueeze(0)
+            res = self.post_processor.process_padded(m["boxes"].unsqueeze(0), m["scores"].unsqueeze(0), m["count"][:1], text, one,
+                                                     [(height, width)], extra)[0]
+        else:
+            res = Instances((height, width))
+            res.pred_boxes = RotatedBoxes(m["boxes"][:n_out])
+            res.scores = m["scores"][:n_out]
+            res.pred_classes = torch.zeros((n_out,), dtype=torch.int64, device=dev)
+            for name, t in (("orientations", orient), ("pred_text_prob", text), ("pred_text_dist", text_dist),
+                            ("pred_view_votes", votes), ("pred_view", view_of), ("pred_view_mask", mask)):
+                if t is not None:
+                    res.set(name, t[0, :n_out])
+            if rois is not None:
+                res.pred_mask_rois = rois[0, :n_out]
+                res.pred_mask_boxes = res.pred_boxes.tensor.clone()
+        self.logger.info(f"Fused views: {V} views, {n_kept} distinct detections, {n_out} with at least {min_votes} votes, "
+                         f"{len(res)} word instances")
         return res
 
     def __call__(self, original_image: np.ndarray) -> Instances:

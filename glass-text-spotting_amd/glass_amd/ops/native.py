@@ -1798,6 +1798,79 @@ def merge_views(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.Tensor,
     return {"boxes": ob, "scores": os_, "src": src, "count": cnt}
 
 
+FUSE_VIEWS_MAX_VIEWS = 64        # csrc/view_fuse.hip FV_VMAX: a view is a bit of the 64-bit view mask
+FUSE_VIEWS_MAX_SLOTS = 8192      # V * K of one fusion: NMS_SMAX, as for merge_views
+FUSE_VIEWS_MAX_OUT = 1024        # NMS_KEEP_MAX = POSTPROCESS_MAX_K: what the word post-processor takes per image
+_FUSE_RANKS = {"detection": 0, "product": 1, "word": 2}
+
+
+def fuse_views(boxes: torch.Tensor, scores: torch.Tensor, counts: torch.Tensor, view_affine: torch.Tensor, bounds: torch.Tensor,
+               nms_thresh: float, text_arg: Optional[torch.Tensor] = None, text_max: Optional[torch.Tensor] = None,
+               stop_index: int = 0, rank: str = "detection", min_votes: int = 1, max_out: int = FUSE_VIEWS_MAX_OUT) -> dict:
+    """The padded detections of V rotated / rescaled views of ONE image -> one detection set in the image's frame, each row
+    with the views that found it (glass_fuse_views, include/glass_hip_feature_fuse.h has the contract): boxes [V,K,5] in each
+    view's pixels, scores [V,K], counts int32 [V], view_affine float64 [V,8] (m0..m5, s, dtheta: inference.view_fusion.plan_views
+    makes the rows), bounds [4] (x0, y0, x1, y1, may be +-inf), all on the device; `rank` "detection" | "product" | "word" picks
+    the key by which the copies of a word compete, and the last two need text_arg int32 / text_max float32 [V,K,T] (what
+    text_argmax returns) and the stop symbol's index.  Returns {"boxes" [max_out,5], "scores", "keys" [max_out], "src" int32
+    [max_out] = v*K + s, "votes" int32 [max_out], "views" int64 [max_out] (bit v: view v), "count" int32 [3] = (rows, truncated,
+    kept before the vote filter)} as views of one zeroed buffer.  Stream-ordered, no read-back; a wrong shape, dtype, device or
+    limit is a ValueError before any launch."""
+    if rank not in _FUSE_RANKS:
+        raise ValueError(f"fuse_views: rank={rank!r} (one of {', '.join(_FUSE_RANKS)})")
+    mode = _FUSE_RANKS[rank]
+    named = [("boxes", boxes, torch.float32), ("scores", scores, torch.float32), ("counts", counts, torch.int32),
+             ("view_affine", view_affine, torch.float64), ("bounds", bounds, torch.float32)]
+    if mode != 0 or text_arg is not None or text_max is not None:
+        named += [("text_arg", text_arg, torch.int32), ("text_max", text_max, torch.float32)]
+    for name, t, dt in named:
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dt or not t.is_contiguous():
+            raise ValueError(f"fuse_views: {name} must be a contiguous {dt} tensor on the device (got "
+                             f"{getattr(t, 'dtype', type(t))} on {getattr(t, 'device', None)})")
+        if t.device != boxes.device:
+            raise ValueError(f"fuse_views: {name} is on {t.device}, boxes on {boxes.device}")
+    if boxes.dim() != 3 or boxes.shape[2] != 5:
+        raise ValueError(f"fuse_views: boxes {tuple(boxes.shape)}: needs [V, K, 5]")
+    V, K = int(boxes.shape[0]), int(boxes.shape[1])
+    for name, t, shape in (("scores", scores, (V, K)), ("counts", counts, (V,)), ("view_affine", view_affine, (V, 8)),
+                           ("bounds", bounds, (4,))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f"fuse_views: {name} {tuple(t.shape)}: needs {shape}")
+    T = 1
+    if text_arg is not None:
+        if text_arg.dim() != 3 or tuple(text_arg.shape[:2]) != (V, K) or text_max.shape != text_arg.shape:
+            raise ValueError(f"fuse_views: text_arg {tuple(text_arg.shape)}, text_max {tuple(text_max.shape)}: need [{V}, {K}, T]")
+        T = int(text_arg.shape[2])
+        if not 1 <= T <= 64:
+            raise ValueError(f"fuse_views: T={T} decoding steps (1..64)")
+    if V > FUSE_VIEWS_MAX_VIEWS or not 1 <= K <= FUSE_VIEWS_MAX_OUT or V * K > FUSE_VIEWS_MAX_SLOTS:
+        raise ValueError(f"fuse_views: V={V} views of K={K} slots: needs V <= {FUSE_VIEWS_MAX_VIEWS}, 1 <= K <= "
+                         f"{FUSE_VIEWS_MAX_OUT} and V * K <= {FUSE_VIEWS_MAX_SLOTS}")
+    max_out, min_votes, stop_index, nms_thresh = int(max_out), int(min_votes), int(stop_index), float(nms_thresh)
+    if not 1 <= max_out <= FUSE_VIEWS_MAX_OUT:
+        raise ValueError(f"fuse_views: max_out={max_out} (1..{FUSE_VIEWS_MAX_OUT})")
+    if not 1 <= min_votes <= FUSE_VIEWS_MAX_VIEWS:
+        raise ValueError(f"fuse_views: min_votes={min_votes} (1..{FUSE_VIEWS_MAX_VIEWS})")
+    if stop_index < 0:
+        raise ValueError(f"fuse_views: stop_index={stop_index}")
+    if not math.isfinite(nms_thresh):
+        raise ValueError(f"fuse_views: nms_thresh={nms_thresh} is not finite")
+    dev = boxes.device
+    # (every view of zeros_views starts 16-byte aligned: the int64 masks are two int32 words each)
+    ob, os_, ok, src, votes, views, cnt = zeros_views([((max_out, 5), torch.float32), ((max_out,), torch.float32),
+                                                        ((max_out,), torch.float32), ((max_out,), torch.int32),
+                                                        ((max_out,), torch.int32), ((2 * max_out,), torch.int32),
+                                                        ((3,), torch.int32)], dev)
+    views = views.view(torch.int64)
+    ws_bytes = int(lib().glass_fuse_views_workspace_bytes(V, K))
+    ws = _workspace(ws_bytes, dev)                   # needs no initialisation
+    check(lib().glass_fuse_views(_dev(boxes), _dev(scores), _dev(counts), _opt(text_arg if mode else None),
+                                 _opt(text_max if mode else None), T, stop_index, mode, _dev(view_affine), _dev(bounds), V, K,
+                                 nms_thresh, min_votes, max_out, _dev(ob), _dev(os_), _dev(ok), _dev(src), _dev(votes), _dev(views),
+                                 _dev(cnt), _dev(ws), ws_bytes, stream_handle()), "glass_fuse_views")
+    return {"boxes": ob, "scores": os_, "keys": ok, "src": src, "votes": votes, "views": views, "count": cnt}
+
+
 LEXICON_MAX_QUERY = 64       # symbols of one query: the bit-parallel pattern is one 64-bit word
 
 
